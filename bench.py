@@ -10,7 +10,15 @@ fp32), one process per GPU, weak scaling.
 A step = zero grads, forward and backward of DiffTransformerEncoderGenGCN (all layers, attention
 -> coefficient generator -> spectral filter on the last layer -> linear_cat) on one batch that is
 already resident in HBM, plus, for N > 1, the RCCL all-reduce of the flat gradient bucket.
-Rank 0 prints ONE JSON line (contract in the task description) with these extra objects:
+Rank 0 prints ONE JSON line: metric, value (graphs/s), unit, higher_is_better, dtype, ms_per_step
+(milliseconds of one timed step), steps, warmup and the configuration.  A plain run does only that: set-up,
+W warm-up steps, K timed steps, the line.
+
+    --dump-outputs DIR  after the timed steps, rank 0 writes what the last step computed - the encoder
+                        output (out.npy) and every parameter gradient (grad.<name>.npy) - as float32 .npy
+                        files (a fixed, seeded sample of each array beyond 64 MB in all); the inputs are
+                        seeded, so two builds can be compared output for output
+    --full              everything else the benchmark measures, as further objects of the same line:
   roofline           the dominant hand-written kernel SYMBOL of the step (largest launches x time), timed
                      live with HIP events in the variants the stack issues
   roofline_streaming the north-star kernel (U^T X -> g(Lambda) -> U) at a batch beyond the Infinity Cache
@@ -18,6 +26,9 @@ Rank 0 prints ONE JSON line (contract in the task description) with these extra 
   reference_literal  the reference-literal operator (filter_mode='cheb': order-P Chebyshev recursion,
                      heads_share_graph=False: transformer/models.py:186) timed the same way, with its own
                      cpu_baseline (the reference-faithful restatement)
+  bf16_leg, two_phase_n1, extra_configs
+                     the same step on bf16 storage, the split backward on one GPU, and BASELINE configs
+                     4 / 5 (fp32 headline run at the default shape only)
 """
 import argparse
 import json
@@ -110,6 +121,12 @@ def parse(argv=None):
                     help='LAUNCHER REHEARSAL, not a measurement: the same step() on CPU tensors through the host '
                          'SIMT emulation of the kernels (tools/simt, test hook) with the gloo backend; the line it '
                          'prints carries "invalid"')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline objects, the CPU baselines, the reference-literal operator and the further '
+                         'legs / configurations (bf16_leg, two_phase_n1, extra_configs); a plain run times the headline '
+                         'step only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's encoder output and parameter gradients to DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -363,6 +380,28 @@ def time_steps(step, args, world, dev):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     return float(tmax.item())
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, step, enc):
+    """What a caller of the timed step receives after its last replay - the encoder output and the parameter
+    gradients - as float32 (float64 stays float64) DIR/<name>.npy.  Beyond DUMP_MAX_BYTES in all, every array keeps
+    its share of the budget as a fixed, seeded sample of its flattened elements (sorted indices)."""
+    import numpy as np
+    arrays = [('out', step.held['out'])]
+    arrays += [('grad.' + n, p.grad) for n, p in enc.named_parameters() if p.grad is not None]
+    arrays = [(n, t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()) for n, t in arrays]
+    total = sum(t.numel() * t.element_size() for _, t in arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, t.numel() * DUMP_MAX_BYTES // total)
+            g = torch.Generator().manual_seed(0)
+            t = t.reshape(-1)[torch.randperm(t.numel(), generator=g)[:keep].sort().values]
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
+    log('outputs of the last step written to %s (%d arrays)' % (path, len(arrays)))
 
 
 def time_kernel(fn, iters):
@@ -723,11 +762,13 @@ def main(argv=None):
     log('graph captured' if use_graph else 'eager mode')
     dt = time_steps(step, args, world, dev)
     log('timed region done: %.3f ms/step' % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, enc)
 
     # beside the headline leg (N = 1, fp32 run only): the bf16 storage leg of BASELINE configs 3 / 5 on the same batch,
     # and the split backward --gpus N uses, so that the first SCALE run has its single-GPU baseline
     extra = {}
-    if world == 1 and not args.dry_cpu and args.dtype == 'f32' and not args.no_literal:
+    if args.full and world == 1 and not args.dry_cpu and args.dtype == 'f32' and not args.no_literal:
         import copy
         a16 = copy.copy(args)
         a16.dtype = 'bf16'
@@ -758,8 +799,8 @@ def main(argv=None):
     # BASELINE configs 4 and 5 as further objects of the same line (parity-test shapes, not the metric): PATTERN
     # (B = 64, N_pad = 128, K = 32; experiments/run_transformer_gengcn_SBM_cv.py) and the molhiv bucket (B = 1024,
     # N_pad = 64, bf16 storage), each timed like the headline leg and with the roofline object of its own dominant kernel
-    if (world == 1 and not args.dry_cpu and args.dtype == 'f32' and not args.no_literal and args.shape == 'zinc'
-            and args.batch == 128):
+    if (args.full and world == 1 and not args.dry_cpu and args.dtype == 'f32' and not args.no_literal
+            and args.shape == 'zinc' and args.batch == 128):
         import copy
         extra['extra_configs'] = []
         ref_default = dict(layer_norm=True, no_pe=True)    # what README.md:49,65,71 run: no --batch-norm, no --pos-enc
@@ -801,7 +842,7 @@ def main(argv=None):
             del gpux, encx, stepx
 
     literal = None
-    if (not args.no_literal and not args.dry_cpu and args.dtype == 'f32'
+    if (args.full and not args.no_literal and not args.dry_cpu and args.dtype == 'f32'
             and not (args.filter_mode == 'cheb' and args.no_share_graph)):
         # the reference-literal operator on the same batch, same parameters, timed the same way
         enc_lit = build_encoder(args, filter_mode='cheb', share=False).to(dev)
@@ -845,8 +886,9 @@ def main(argv=None):
             res['note'] = ('bf16 storage leg (BASELINE configs 3 / 5): bf16 token tensors and LDS tiles, fused stack on '
                            'v_mfma_f32_16x16x16_bf16, fp32 statistics / parameter gradients / filter stage; the headline '
                            'line is --dtype f32 (the reference\'s arithmetic)')
-            res['roofline'] = roofline(args, gpu, dev, lowp=True)
-        else:
+            if args.full:
+                res['roofline'] = roofline(args, gpu, dev, lowp=True)
+        elif args.full:
             res['roofline'] = roofline(args, gpu, dev)
             if args.stream_batch > 0:
                 res['roofline_streaming'] = roofline_streaming(args, dev)

@@ -8,7 +8,7 @@ OUT=gpurun_out/${1:-prof}
 mkdir -p $OUT
 export TMPDIR=/tmp
 P="rocprofv3 --output-format csv"
-BF="--steps 50 --warmup 10 --no-cpu-baseline --no-literal --stream-batch 0 --kernel-iters 1"
+BF="--full --steps 50 --warmup 10 --no-cpu-baseline --no-literal --stream-batch 0 --kernel-iters 1"
 $P --kernel-trace --stats -d $OUT/bench -- python3 bench.py $BF > $OUT/bench.json 2> $OUT/bench.err
 $P --kernel-trace --stats -d $OUT/bench_bf16 -- python3 bench.py $BF --dtype bf16 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
 echo "bench traces done"
