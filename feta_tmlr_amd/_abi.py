@@ -259,7 +259,32 @@ SIGNATURES.update({
     'feta_ffn_bwd_coeff': ([C.POINTER(FfnGrad), C.POINTER(CoeffBwdRole), _S], C.c_int),
 })
 
-ABI_VERSION = 11
+class EncoderLayer(C.Structure):
+    """struct feta_encoder_layer (include/feta_hip.h) - field order must match the header."""
+    _fields_ = [
+        ('w_in', _F), ('b_in', _F), ('w_out', _F), ('b_out', _F),
+        ('n1_gamma', _F), ('n1_beta', _F), ('n1_mean', _F), ('n1_var', _F),
+        ('w1', _F), ('b1', _F), ('w2', _F), ('b2', _F),
+        ('n2_gamma', _F), ('n2_beta', _F), ('n2_mean', _F), ('n2_var', _F),
+        ('n1_eps', C.c_float), ('n2_eps', C.c_float), ('tie_qk', C.c_int),
+    ]
+
+
+class EncoderInfer(C.Structure):
+    """struct feta_encoder_infer (include/feta_hip.h) - field order must match the header."""
+    _fields_ = [
+        ('x', _F), ('row_sb', C.c_int64), ('row_sn', C.c_int64), ('pe', _F), ('n_real', _I), ('rowscale', _F),
+        ('y', _F), ('out', _F), ('attn', _F), ('B', C.c_int), ('N', C.c_int), ('H', C.c_int), ('FF', C.c_int),
+        ('L', C.c_int), ('norm', C.c_int), ('layers', C.c_void_p),
+    ]
+
+
+SIGNATURES.update({
+    'feta_encoder_infer_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+    'feta_encoder_infer': ([C.POINTER(EncoderInfer), _S], C.c_int),
+})
+
+ABI_VERSION = 12
 
 
 class FetaError(RuntimeError):
@@ -844,6 +869,32 @@ class Abi:
         self._check(self.lib.feta_spectral_kernel(_p(u), _p(lam), _p(n_real), mode, beta, p, lam_offset,
                                                   int(zero_diag), _p(out), b, n, k, stream),
                     'feta_spectral_kernel')
+
+    def encoder_infer_supported(self, n, d_model, heads, ff, nl):
+        return bool(self.lib.feta_encoder_infer_supported(n, d_model, heads, ff, nl))
+
+    def encoder_infer(self, b, n, heads, ff, layers, layer_norm, stream, seq_first=True, **ptrs):
+        """feta_encoder_infer (ABI 12): the whole stack's forward for inference in one launch.  layers: one dict per
+        layer - tensors for the pointer fields of feta_encoder_layer, n1_eps / n2_eps / tie_qk as numbers;
+        tensor-valued keyword arguments (x, pe, n_real, rowscale, y, out, attn) become the descriptor's pointers."""
+        table = (EncoderLayer * len(layers))()
+        for e, lp in zip(table, layers):
+            for k, v in lp.items():
+                if torch.is_tensor(v):
+                    _same_dtype(torch.float32, v)
+                    setattr(e, k, v.data_ptr())
+                elif v is not None:
+                    setattr(e, k, v)
+        d = EncoderInfer()
+        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
+        d.norm = 1 if layer_norm else 0
+        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k != 'n_real'))
+        for k, t in ptrs.items():
+            if t is not None:
+                setattr(d, k, t.data_ptr())
+        d.layers = C.cast(table, C.c_void_p)
+        self._check(self.lib.feta_encoder_infer(C.byref(d), stream), 'feta_encoder_infer')
 
 
 def bind(cdll):

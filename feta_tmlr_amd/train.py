@@ -277,13 +277,19 @@ def rocauc(scores, labels):
     return float((ranks[y > 0.5].sum() - pos * (pos + 1) / 2.0) / (pos * neg))
 
 
-@torch.no_grad()
-def evaluate(task, model, criterion, batches):
+def evaluate(task, model, criterion, batches, inference_mode=False):
     """The reference's eval_epoch for one split: ``batches`` yields (batch9, graph_cache).  Returns a dict:
     'loss' (sample-weighted mean, as running_loss / n_sample) plus 'mae' and 'mse' (zinc,
     run_transformer_gengcn.py:167-209), 'acc' (tu: fraction of graphs; sbm: mean per-class recall in
     percent averaged over batches, ..._SBM_cv.py:221-266) or 'rocauc' (molhiv).  The model is put in eval
-    mode (BatchNorm running statistics) and restored."""
+    mode (BatchNorm running statistics) and restored.  Runs under torch.no_grad(), or under
+    torch.inference_mode() with inference_mode=True: the encoder stack is then ONE forward-only launch where its
+    shape allows (fused_stack.encoder_stack_infer)."""
+    with torch.inference_mode() if inference_mode else torch.no_grad():
+        return _evaluate(task, model, criterion, batches)
+
+
+def _evaluate(task, model, criterion, batches):
     was_training = model.training
     model.eval()
     tot = {'loss': 0.0, 'mae': 0.0, 'mse': 0.0, 'hit': 0.0, 'acc_sum': 0.0}

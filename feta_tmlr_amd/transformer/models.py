@@ -21,7 +21,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import functional as FF
-from ..fused_stack import StackTail, fused_encoder_stack, stack_supported
+from ..fused_stack import StackTail, encoder_stack_infer, fused_encoder_stack, infer_supported, stack_supported
 from ..parallel import mark_row_constant
 from .ChebNetDynamic import ChebConvDynamic
 from .data import GraphBatchCache
@@ -230,7 +230,10 @@ class DiffTransformerEncoderGenGCN(nn.Module):
                 raise NotImplementedError("the bf16 storage path runs filter_mode='spectral' with matrix coefficients")
             output = output.to(self.storage_dtype)
             pe = None if pe is None else pe.to(self.storage_dtype)    # once for all layers
-        fused = (self.fused_stack and self.last_layer_filter and mask is None
+        # inference (torch.inference_mode): the whole stack as ONE forward-only launch where the shape allows
+        infer = (torch.is_inference_mode_enabled() and not lowp and self.fused_stack and self.last_layer_filter
+                 and mask is None and output.dtype == torch.float32 and infer_supported(self.layers, n, src.shape[-1]))
+        fused = (not infer and self.fused_stack and self.last_layer_filter and mask is None
                  and stack_supported(self.layers, src.shape[-1]))
         if lowp and fused:
             # bf16 storage: the stack runs the bf16 instantiations of the four fused kernels where the shape has them
@@ -260,19 +263,23 @@ class DiffTransformerEncoderGenGCN(nn.Module):
         for layer_num, mod in enumerate(self.layers):
             last = layer_num + 1 == self.num_layers
             filt = last or not self.last_layer_filter                            # :169-171
-            if fused:
-                # every layer in one autograd node (feta_tmlr_amd/fused_stack.py); the loop body
-                # below then only runs the filter stage of the last layer
+            if fused or infer:
+                # every layer in one autograd node (feta_tmlr_amd/fused_stack.py) - or, for inference, in one launch;
+                # the loop body below then only runs the filter stage of the last layer
                 if not last:
                     continue
-                output, concat, attn = fused_encoder_stack(output, pe, degree_rows, cache.n_real,
-                                                           self.layers, need_attn=True, tail=tail, pending=pending)
-                if self.keep_stack_boundary:   # for backward_head / backward_stack
-                    self._stack_boundary = (output, concat)
-                elif pending is not None and concat.requires_grad:
-                    # one backward pass runs the filter stage and then the stack: the stack's reduction launch takes
-                    # the stage's column sums (two passes: the head gradients must be final when the first returns)
-                    pending.stack_armed = True
+                if infer:
+                    output, concat, attn = encoder_stack_infer(output, pe, degree_rows, cache.n_real, self.layers,
+                                                               need_attn=True)
+                else:
+                    output, concat, attn = fused_encoder_stack(output, pe, degree_rows, cache.n_real,
+                                                               self.layers, need_attn=True, tail=tail, pending=pending)
+                    if self.keep_stack_boundary:   # for backward_head / backward_stack
+                        self._stack_boundary = (output, concat)
+                    elif pending is not None and concat.requires_grad:
+                        # one backward pass runs the filter stage and then the stack: the stack's reduction launch takes
+                        # the stage's column sums (two passes: the head gradients must be final when the first returns)
+                        pending.stack_armed = True
                 nn_, bb_, dd_ = concat.shape
                 out_each_head = concat.view(nn_, bb_, self.num_heads, dd_ // self.num_heads).permute(1, 0, 2, 3)
             else:

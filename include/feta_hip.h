@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FETA_ABI_VERSION 11
+#define FETA_ABI_VERSION 12
 
 #define FETA_OK 0
 #define FETA_E_ARG (-1)     /* bad shape / stride / alignment / unsupported size */
@@ -724,6 +724,63 @@ typedef struct feta_coeff_bwd_role {
   int B, N, H, C;
 } feta_coeff_bwd_role;
 int feta_ffn_bwd_coeff(const feta_ffn_grad* d, const feta_coeff_bwd_role* c, feta_stream_t stream);
+
+/* ---- the whole encoder stack for inference in ONE launch (ABI 12) ------------------------------------------
+ * Forward of L DiffTransformerEncoderLayers (contract transformer/models.py:166-167,179,244; body per upstream GraphiT,
+ * README.md:129) with nothing saved for a backward pass: in eval mode nothing couples two graphs (BatchNorm with running
+ * statistics is a per-channel affine, LayerNorm is row-local, attention is per graph), so one workgroup runs every layer
+ * of one graph with the activations in LDS.  Per layer:
+ *   qkv = x W_in^T (+ b_in); attention core exactly as feta_attn_fwd (scale d_h^-1/2, keys >= n_real masked,
+ *   exp(s - rowmax), * pe, / max(rowsum, 1e-6)); y1 = x + rowscale * (concat W_out^T + b_out); x1 = norm1(y1);
+ *   y2 = x1 + relu(x1 W1^T + b1) W2^T + b2; x = norm2(y2)
+ * norm: FETA_NORM_BATCH (eval BatchNorm: (v - running_mean) * rsqrt(running_var + eps) * gamma + beta) or
+ * FETA_NORM_LAYER (affine LayerNorm of the row, biased variance, as F.layer_norm).
+ * Rows of the [M = B*N, 64] tensors x, y, out are row(b, i) = b*row_sb + i*row_sn (seq-first [N,B,64]: row_sb = 1,
+ * row_sn = B); padded rows i >= n_real are computed like every other row.  Only the last layer writes: y (after norm2),
+ * out (its concatenated heads: out_each_head, transformer/models.py:179) and attn [B,H,N,N] (nullable).
+ * feta_encoder_infer_supported: d_model = 64, heads in {4, 8}, 1 <= N <= 64, ff in {64, 128},
+ * 1 <= L <= FETA_ENCODER_MAX_LAYERS.  The layer table is copied into the kernel arguments: `layers` is a HOST pointer,
+ * read during the call only (the launch stays capturable). */
+#define FETA_ENCODER_MAX_LAYERS 16
+#define FETA_NORM_BATCH 0
+#define FETA_NORM_LAYER 1
+typedef struct feta_encoder_layer {
+  const float* w_in;      /* [192,64] */
+  const float* b_in;      /* [192] or NULL */
+  const float* w_out;     /* [64,64] */
+  const float* b_out;     /* [64] or NULL */
+  const float* n1_gamma;  /* [64] norm1 weight */
+  const float* n1_beta;   /* [64] norm1 bias */
+  const float* n1_mean;   /* [64] norm1 running_mean (BatchNorm; NULL for LayerNorm) */
+  const float* n1_var;    /* [64] norm1 running_var (BatchNorm; NULL for LayerNorm) */
+  const float* w1;        /* [ff,64] */
+  const float* b1;        /* [ff] or NULL */
+  const float* w2;        /* [64,ff] */
+  const float* b2;        /* [64] or NULL */
+  const float* n2_gamma;
+  const float* n2_beta;
+  const float* n2_mean;
+  const float* n2_var;
+  float n1_eps, n2_eps;
+  int tie_qk;             /* 1: K = Q (before the scale); rows 64..127 of w_in / b_in are not read */
+} feta_encoder_layer;
+
+struct feta_encoder_infer {   /* (a struct tag only: the entry point has the same name) */
+  const float* x;         /* [M,64] input of the first layer */
+  int64_t row_sb, row_sn;
+  const float* pe;        /* [B,N,N] or NULL (broadcast over heads) */
+  const int32_t* n_real;  /* [B] */
+  const float* rowscale;  /* [M] degree scale per row, or NULL */
+  float* y;               /* [M,64] output of the last layer */
+  float* out;             /* [M,64] concatenated heads of the last layer */
+  float* attn;            /* [B,H,N,N] of the last layer, or NULL */
+  int B, N, H, FF, L;
+  int norm;               /* FETA_NORM_BATCH | FETA_NORM_LAYER, every layer alike */
+  const feta_encoder_layer* layers;  /* HOST pointer to L layer structs */
+};
+
+int feta_encoder_infer_supported(int N, int d_model, int heads, int ff, int L);
+int feta_encoder_infer(const struct feta_encoder_infer* d, feta_stream_t stream);
 
 /* ---- graph preprocessing -------------------------------------------------------------
  * Dense Lhat = -D^-1/2 A D^-1/2 per graph from the batched edge list, with the exact
