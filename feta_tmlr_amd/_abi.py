@@ -172,7 +172,7 @@ class AttnBlock(C.Structure):
         ('rowscale', _F), ('qkv', _F), ('out', _F), ('attn_stats', _F), ('attn', _F), ('y', _F),
         ('y_stats', _F), ('scale', C.c_float), ('B', C.c_int), ('N', C.c_int), ('M', C.c_int),
         ('row_sb', C.c_int64), ('row_sn', C.c_int64), ('tie_qk', C.c_int), ('dtype', C.c_int), ('y_shift', _F),
-        ('out_f32', _F), ('x_ln_gamma', _F), ('x_ln_beta', _F),
+        ('out_f32', _F), ('x_ln_gamma', _F), ('x_ln_beta', _F), ('H', C.c_int),
     ]
 
 
@@ -229,7 +229,7 @@ class AttnBlockGrad(C.Structure):
         ('pe', _F), ('n_real', _I), ('attn_stats', _F), ('x0', _F), ('bn0', _F), ('dx', _F), ('dx_b', _F), ('sum_out', _F),
         ('partial', _F), ('partial_ld', C.c_int), ('scale', C.c_float), ('B', C.c_int), ('N', C.c_int), ('M', C.c_int),
         ('row_sb', C.c_int64), ('row_sn', C.c_int64), ('dtype', C.c_int), ('dout2_f32', C.c_int),
-        ('ln1_gamma', _F), ('x0_ln_gamma', _F), ('x0_ln_beta', _F), ('ln_eps', C.c_float),
+        ('ln1_gamma', _F), ('x0_ln_gamma', _F), ('x0_ln_beta', _F), ('ln_eps', C.c_float), ('H', C.c_int),
     ]
 
 
@@ -284,7 +284,7 @@ SIGNATURES.update({
     'feta_encoder_infer': ([C.POINTER(EncoderInfer), _S], C.c_int),
 })
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class FetaError(RuntimeError):
@@ -665,14 +665,15 @@ class Abi:
         return int(self.lib.feta_attn_block_stat_rows(b, n))
 
     def attn_block_fwd(self, b, n, scale, stream, seq_first=True, momentum=0.1, eps=1e-5, Gx=0, tie_qk=False,
-                       sums=(), **ptrs):
-        """feta_attn_block_fwd; tensor-valued keyword arguments become the descriptor's pointers."""
-        self.attn_block_launch(self.attn_block_desc(b, n, scale, seq_first, momentum, eps, Gx, tie_qk, **ptrs),
+                       sums=(), heads=4, **ptrs):
+        """feta_attn_block_fwd; tensor-valued keyword arguments become the descriptor's pointers.  heads: 4 (d_h = 16)
+        or 8 (d_h = 8, fp32 storage; attn_stats / attn then have 8 heads)."""
+        self.attn_block_launch(self.attn_block_desc(b, n, scale, seq_first, momentum, eps, Gx, tie_qk, heads=heads, **ptrs),
                                stream, sums)
 
-    def attn_block_desc(self, b, n, scale, seq_first=True, momentum=0.1, eps=1e-5, Gx=0, tie_qk=False, **ptrs):
+    def attn_block_desc(self, b, n, scale, seq_first=True, momentum=0.1, eps=1e-5, Gx=0, tie_qk=False, heads=4, **ptrs):
         d = AttnBlock()
-        d.B, d.N, d.M, d.scale = b, n, b * n, scale
+        d.B, d.N, d.M, d.scale, d.H = b, n, b * n, scale, heads
         d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
         d.momentum, d.eps, d.Gx, d.tie_qk = momentum, eps, Gx, int(tie_qk)
         d.dtype = _stack_dtype(ptrs, ('x', 'pe', 'qkv', 'out', 'y'))
@@ -712,11 +713,11 @@ class Abi:
         return int(self.lib.feta_attn_block_bwd_blocks(b))
 
     def attn_block_bwd(self, b, n, scale, stream, seq_first=True, Gs=0, partial_ld=0, partial_ptr=None, sums=(), ln_eps=1e-5,
-                       **ptrs):
+                       heads=4, **ptrs):
         """feta_attn_block_bwd; tensor-valued keyword arguments become the descriptor's pointers.  sums: [(in [R, C],
         out [C])] column sums that ride in trailing workgroups of the launch (feta_attn_block_bwd_sums)"""
         d = AttnBlockGrad()
-        d.B, d.N, d.M, d.scale, d.Gs, d.partial_ld, d.ln_eps = b, n, b * n, scale, Gs, partial_ld, ln_eps
+        d.B, d.N, d.M, d.scale, d.Gs, d.partial_ld, d.ln_eps, d.H = b, n, b * n, scale, Gs, partial_ld, ln_eps, heads
         d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
         if partial_ptr is not None:
             d.partial = partial_ptr

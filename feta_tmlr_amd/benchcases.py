@@ -29,7 +29,8 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
     def prm_of(c):
         return prm[:, :c].contiguous()
 
-    if abi.attn_block_supported(n, d, heads):
+    blk_dt = heads == 4 or dtype == torch.float32     # (8 heads: fp32 storage only)
+    if abi.attn_block_supported(n, d, heads) and blk_dt:
         x, w_in, b_in = rndt(m, d), rnd(3 * d, d) / d ** 0.5, rnd(3 * d)
         w_o, b_o, deg = rnd(d, d) / d ** 0.5, rnd(d), torch.rand(m, generator=g).to(dev)
         qkv, out, y1, st1 = newt(m, 3 * d), newt(m, d), newt(m, d), new(abi.attn_block_stat_rows(b, n) + 1, 2, d)
@@ -42,8 +43,8 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
         base_o = b * 2 * heads * n + 4 * d * d                                                    # fp32 elements
         scale = dh ** -0.5
         # descriptors are built once: the eager timing loop must not be bound by Python
-        d0 = abi.attn_block_desc(b, n, scale, attn=None, **common)
-        d1 = abi.attn_block_desc(b, n, scale, attn=attn, **common)
+        d0 = abi.attn_block_desc(b, n, scale, attn=None, heads=heads, **common)
+        d1 = abi.attn_block_desc(b, n, scale, attn=attn, heads=heads, **common)
         cases.append(('attn_block_fwd (no attn write)', 1.0,
                       lambda: (abi.attn_block_launch(d0, st), common)[0], ft * base_t + f4 * base_o,
                       ['attn_block_fwd']))
@@ -147,7 +148,7 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
                   bn0=prm_of(d), dx=dx, sum_out=new(2 * gb, 2, d))
         keep_a = (kw, part)
         cases.append(('attn_block_bwd', 1.0,
-                      lambda: (abi.attn_block_bwd(b, n, dh ** -0.5, st, Gs=G, partial_ptr=part.data_ptr(), partial_ld=cols,
+                      lambda: (abi.attn_block_bwd(b, n, dh ** -0.5, st, heads=heads, Gs=G, partial_ptr=part.data_ptr(), partial_ld=cols,
                                                   **kw), keep_a)[0],
                       ft * (8 * m * d + (b * n * n if pe is not None else 0)) + f4 * (2 * b * heads * n + 4 * d * d + gb * cols),
                       ['attn_block_bwd<false>']))
@@ -156,7 +157,7 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
             kws = dict(kw, dx_b=newt(m, d))
             keep_s = (kws, part)
             cases.append(('attn_block_bwd (two workgroups per graph)', 1.0,
-                          lambda: (abi.attn_block_bwd(b, n, dh ** -0.5, st, Gs=G, partial_ptr=part.data_ptr(),
+                          lambda: (abi.attn_block_bwd(b, n, dh ** -0.5, st, heads=heads, Gs=G, partial_ptr=part.data_ptr(),
                                                       partial_ld=cols, **kws), keep_s)[0],
                           ft * (9 * m * d + (b * n * n if pe is not None else 0)) + f4 * (2 * b * heads * n + 4 * d * d + b * cols),
                           ['attn_block_bwd<true>']))

@@ -320,5 +320,6 @@ extern "C" int feta_attn_out_fwd_sums(const feta_attn_block* d, const feta_colsu
   // (the kernel is written against the storage policy of feta_lp.h, but the bf16 layer stack stops at N <= 64 - shapes
   // beyond run its op-by-op path - so only the fp32 instantiation is built and tested)
   FETA_REQUIRE(a.dtype == FETA_F32, "attn_out_fwd: fp32 token tensors only (dtype %d)", a.dtype);
+  FETA_REQUIRE(a.H == 0 || a.H == 4, "attn_out_fwd: 4 heads only (H=%d; the 8-head form is feta_attn_block, N <= 64)", a.H);
   return dispatch_attn_out<float>(a, segs, nseg, (hipStream_t)stream);
 }

@@ -2,6 +2,9 @@
 // BASELINE shape (d = 64 = 4 heads x 16, N <= 64): in_proj -> attention core -> out_proj ->
 // degree scale -> residual -> BatchNorm statistics (contract transformer/models.py:166-167,179,244;
 // body per upstream GraphiT, README.md:129).  One workgroup per graph, one wave per head.
+// ABI 13 (feta_attn_block.H = 8): the eight-wave kernel below also runs d = 64 = 8 heads x 8 (fp32 storage) - a wave's
+// 16-column tile then holds two heads (TWO); every instantiation of it is spill-free.  The four-wave kernel, the bf16
+// instantiations and feta_attn_out (N > 64, csrc/attnout.hip) stay 4 heads x 16.
 //
 // The three stages share everything on chip:
 //   * the graph's node rows X_b [N, 64] are fetched once as whole 256-byte rows, normalised on the
@@ -17,6 +20,7 @@
 // q, k, v, the per-head output and the softmax statistics are still written to HBM: the backward
 // pass (attn.hip, rowwise.hip) and the spectral filter read them.
 #include <cstdlib>
+#include <type_traits>
 
 #include "feta_abi_common.h"
 #include "feta_colsum.h"
@@ -499,7 +503,14 @@ __host__ __device__ inline int block8_lds_bytes(int nt) {
   return tot > role ? tot : role;
 }
 
-template <class T, int NT, int WGS>
+// TWO (ABI 13): d_h = 8 - the 16-column tile of a wave holds TWO heads (2h, 2h + 1).  Everything row-wise is expressed
+// per column tile and does not change; the attention core runs once per sub-head `sh`, one after the other over the same
+// K / V / Q tiles and the same score registers: the scores of sub-head sh are the same four MFMA steps with the Q operand
+// zeroed in the lane groups of the other head's features (g >> 1 != sh: a lane group holds features 4g .. 4g+3), and in
+// P.V the B operand's lane lq is the output column, so V is zeroed in the other head's columns (lq >> 3 != sh) and both
+// heads accumulate into the one tile - which already is the concat layout.  Per-head buffers: attn [B,8,N,N], attn_stats
+// [B,8,N,2].  A compile-time flag: the 4-head instantiations are what they were.
+template <class T, int NT, int WGS, bool TWO>
 __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs a, ColsumPlan sums, int main_grid) {
   typedef Lp<T> L;
   typedef typename L::Op Op;
@@ -761,6 +772,8 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
   FETA_STAMP(2);
 
   // ---- attention core of this wave's query tiles (the arithmetic of the four-wave kernel) -----------------------
+  // (the 4-head form is kept as it was, textually: its instantiations compile to what they were)
+  if constexpr (!TWO) {
   const int bh = b * kBlkH + h;
   // (scalars, not f32x4 acc[NQ][NT]: at 32 floats the optimizer promotes such an array to ONE vector value and every
   // conditional tile update copies the whole tuple - see csrc/attnout.hip)
@@ -866,6 +879,123 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
       wave_lds_sync();
     }
   }
+  } else {
+  constexpr int NS = TWO ? 2 : 1;   // heads of this wave's column tile
+  f32x4 o[NQ];   // (both heads of the tile accumulate into it)
+  auto attn_head = [&](auto shc) __attribute__((always_inline)) {
+  constexpr int sh = decltype(shc)::value;
+  const bool ga = (g >> 1) == sh, la = (lq >> 3) == sh;   // this head's features / output columns
+  const int bh = b * (kBlkH * NS) + NS * h + sh;
+  // (scalars, not f32x4 acc[NQ][NT]: at 32 floats the optimizer promotes such an array to ONE vector value and every
+  // conditional tile update copies the whole tuple - see csrc/attnout.hip)
+  float acc[NQ][NT][4];
+#pragma unroll
+  for (int kt = 0; kt < NT; ++kt) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      f32x4 t = zero4();
+      if (16 * kt < n && slot + S * i < NT) t = L::mma(kf[kt], L::sel(ga, qs[i], L::zero()), zero4());  // (key 4g+r, query lq)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][kt][r] = t[r];
+    }
+  }
+  float mx[NQ], zs[NQ], rinv[NQ];
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (16 * kt + 4 * g + r < n) m = fmaxf(m, acc[i][kt][r]);
+    mx[i] = m;
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) mx[i] = fmaxf(mx[i], shfl_xor(mx[i], 16));
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) mx[i] = fmaxf(mx[i], shfl_xor(mx[i], 32));
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) zs[i] = 0.0f;
+  // pe of this lane's (query lq, keys 4g .. 4g+3) pairs: one 16-byte LDS read per tile pair, where it is used
+#pragma unroll
+  for (int kt = 0; kt < NT; ++kt) {
+    if (16 * kt >= n) continue;
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      if (slot + S * i >= NT) continue;
+      const int qc = min(16 * (slot + S * i) + lq, a.N - 1);
+      const float4 t = *reinterpret_cast<const float4*>(Pe + qc * PEP + 16 * kt + 4 * g);
+      const float pv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool kok = 16 * kt + 4 * g + r < n;
+        const float e = kok ? fast_exp(acc[i][kt][r] - mx[i]) * pv[r] : 0.0f;
+        acc[i][kt][r] = e;
+        zs[i] += e;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) zs[i] += shfl_xor(zs[i], 16);
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) zs[i] += shfl_xor(zs[i], 32);
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    rinv[i] = 1.0f / fmaxf(zs[i], 1e-6f);
+    if (sh == 0) o[i] = zero4();
+    const int qb = slot + S * i, q = 16 * qb + lq;
+    if (g == 0 && qb < NT && q < a.N) {
+      float* st = a.attn_stats + ((int64_t)bh * a.N + q) * 2;
+      st[0] = mx[i];
+      st[1] = zs[i];
+    }
+  }
+#pragma unroll
+  for (int kt = 0; kt < NT; ++kt) {
+    if (16 * kt >= n) continue;
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      if (slot + S * i >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][kt][r] *= rinv[i];
+      o[i] = L::mma(L::mk(acc[i][kt][0], acc[i][kt][1], acc[i][kt][2], acc[i][kt][3]),
+                    L::sel(la, vbo[kt], L::zero()), o[i]);  // (query 4g+r, c' lq)
+    }
+  }
+  if (sh == NS - 1) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int qb = slot + S * i;
+      if (qb < NT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) L::st1(Os + (16 * qb + 4 * g + r) * P + DH * h + lq, o[i][r]);
+      }
+    }
+  }
+  if (a.attn != nullptr) {
+    if (sh == 0) lds_barrier();   // the staging area of this wave is the K / V hand-over its sibling may still be reading
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int qb = slot + S * i;
+      if (qb >= NT) continue;
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stg[lq * KP + 16 * kt + 4 * g + r] = acc[i][kt][r];
+      wave_lds_sync();
+      const int rows = min(16, a.N - 16 * qb);
+      float* dst = a.attn + ((int64_t)bh * a.N + 16 * qb) * a.N;
+      for (int j = lane; j < rows * a.N; j += 64) {
+        const int qq = j / a.N, kk = j - qq * a.N;
+        dst[j] = stg[qq * KP + kk];
+      }
+      wave_lds_sync();
+    }
+  }
+  };  // one head of the column tile
+  attn_head(std::integral_constant<int, 0>{});
+  attn_head(std::integral_constant<int, 1>{});
+  }
   FETA_STAMP(3);
   lds_barrier();
   FETA_STAMP(4);
@@ -968,10 +1098,10 @@ static BlockFwdForm block_fwd_form(int B, int N) {
   return f;
 }
 
-template <class T, int NT, int WGS>
+template <class T, int NT, int WGS, bool TWO = false>
 int launch_block_fwd8(const BlockArgs& a, const feta_colsum_seg* segs, int nseg, int cap, hipStream_t stream) {
   const size_t lds = block8_lds_bytes<T>(NT);
-  auto kern = attn_block_fwd8_kernel<T, NT, WGS>;
+  auto kern = attn_block_fwd8_kernel<T, NT, WGS, TWO>;
   static LdsSeen lds_seen;
   allow_dynamic_lds(kern, lds, lds_seen);
   int gp = cap / WGS;   // graphs in flight
@@ -1002,6 +1132,27 @@ int launch_block_fwd(const BlockArgs& a, const feta_colsum_seg* segs, int nseg, 
   if (const char* e = getenv("FETA_BLOCK_WEIGHTS_LAST")) weights_last = atoi(e) != 0 && !(NT == 4 && sizeof(T) == sizeof(float));
   hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kRowThreads), lds, stream, a, plan, grid, weights_last);
   return check_launch("feta_attn_block_fwd");
+}
+
+// 8 heads (d_h = 8, fp32 storage): the eight-wave forms only.  FETA_BLOCK_FWD_WAVES=4 names a kernel that has no such
+// form and is ignored - one workgroup per graph then, so that the y_stats rows are the ones feta_attn_block_stat_rows
+// announced for that setting (a row per graph, the shift row at B).
+static int dispatch_block_fwd_two(const BlockArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
+  BlockFwdForm f = block_fwd_form(a.B, a.N);
+  if (f.waves == 4) {
+    f.wgs = 1;
+    f.cap = a.B;
+  }
+  if (f.wgs == 2) {
+    if ((a.N + 15) / 16 == 3) return launch_block_fwd8<float, 3, 2, true>(a, segs, nseg, f.cap, stream);
+    return launch_block_fwd8<float, 4, 2, true>(a, segs, nseg, f.cap, stream);
+  }
+  switch ((a.N + 15) / 16) {
+    case 1: return launch_block_fwd8<float, 1, 1, true>(a, segs, nseg, f.cap, stream);
+    case 2: return launch_block_fwd8<float, 2, 1, true>(a, segs, nseg, f.cap, stream);
+    case 3: return launch_block_fwd8<float, 3, 1, true>(a, segs, nseg, f.cap, stream);
+    default: return launch_block_fwd8<float, 4, 1, true>(a, segs, nseg, f.cap, stream);
+  }
 }
 
 template <class T>
@@ -1038,7 +1189,7 @@ extern "C" int feta_debug_block_stamps(unsigned long long* out256) {
 #endif
 
 extern "C" int feta_attn_block_supported(int N, int d_model, int heads) {
-  return (d_model == kBlkD && heads == kBlkH && N >= 1 && N <= 64) ? 1 : 0;
+  return (d_model == kBlkD && (heads == 4 || heads == 8) && N >= 1 && N <= 64) ? 1 : 0;
 }
 
 extern "C" int feta_attn_block_stat_rows(int B, int N) {
@@ -1074,6 +1225,11 @@ extern "C" int feta_attn_block_fwd_sums(const feta_attn_block* d, const feta_col
   FETA_REQUIRE(a.x_ln_gamma == nullptr || (a.x_ln_beta != nullptr && a.x_stats == nullptr && a.x_bn == nullptr),
                "attn_block_fwd: x_ln_gamma needs x_ln_beta and excludes x_bn / x_stats");
   FETA_REQUIRE(a.dtype == FETA_F32 || a.dtype == FETA_BF16, "attn_block_fwd: dtype %d", a.dtype);
+  FETA_REQUIRE(a.H == 0 || a.H == 4 || a.H == 8, "attn_block_fwd: H=%d (0 = 4, 4 or 8 heads)", a.H);
+  if (a.H == 8) {
+    FETA_REQUIRE(a.dtype == FETA_F32, "attn_block_fwd: 8 heads need fp32 storage");
+    return dispatch_block_fwd_two(a, segs, nseg, (hipStream_t)stream);
+  }
   if (a.dtype == FETA_BF16) return dispatch_block_fwd<bf16_t>(a, segs, nseg, (hipStream_t)stream);
   return dispatch_block_fwd<float>(a, segs, nseg, (hipStream_t)stream);
 }

@@ -22,7 +22,12 @@
 // g1; dx_b: pair 1) and the consumer adds the two on load (feta_ffn_bwd's dy_b); the partial sums of the previous
 // BatchNorm's backward are linear in dx, so they are emitted per workgroup as well; dW_out columns / dW_in rows of the
 // two pairs are disjoint parts of the graph's partial row.
+//
+// ABI 13 (feta_attn_block_grad.H = 8): d = 64 = 8 heads x 8, fp32 storage - "head" above reads "16-column tile", which
+// then holds two heads (TWO, below); all twelve fp32 instantiations of it (NT x {one workgroup, SPLIT, LOOP}) are
+// spill-free, so no shape keeps the three-launch form.
 #include <cstdlib>
+#include <type_traits>
 
 #include "feta_abi_common.h"
 #include "feta_colsum.h"
@@ -41,11 +46,11 @@ constexpr int kBbMaxGrid = 256;
 
 // LDS bytes of a workgroup: seven [NR][64 + pad] tiles of T, fp32 for everything else
 template <class T>
-__host__ __device__ inline int block_bwd_lds_bytes(int nt, bool gbn, bool gln = false) {
+__host__ __device__ inline int block_bwd_lds_bytes(int nt, bool gbn, bool gln = false, int heads = kBbH) {
   const int nr = 16 * nt, P = kBbD + Lp<T>::PAD;
   return (int)sizeof(T) * 7 * nr * P    // q, k, v (later dq, dk, dv), dconcat, out, g1, x0
          + 4 * (nr * (nr + 1)           // pe
-                + kBbH * nr * 2 + nr    // softmax statistics, row scale
+                + heads * nr * 2 + nr   // softmax statistics, row scale
                 + 8 * kBbD + 8 * 2 * 16 // fp32 column sums of the bias gradients: db_out per wave, dq | dk | dv per wave
                 + (gbn ? 5 * kBbD + reduce_scratch_floats(kBbD, 512) : 0)
                 + (gln ? 8 * 2 * kBbD : 0));   // LayerNorm stack: column sums of (dy xhat1, dy) per wave
@@ -70,7 +75,14 @@ __device__ __forceinline__ void acc_to(float* p, float v, bool first) {
 // parameter blocks and partial sums, softmax statistics, row scale and the weight-gradient partial rows: fp32.
 // LOOP: more graphs than workgroups - a separate instantiation, because the graph loop costs registers (the single-graph
 // forms are spill-free; the compiler treats everything invariant in the loop as hoistable).
-template <class T, int NT, bool SPLIT, bool LOOP>
+// TWO (ABI 13): d_h = 8 - a 16-column tile holds TWO heads (2h, 2h + 1; `h` below is the column tile).  The row-wise
+// products, the weight-gradient partial rows, the statistics and SPLIT (a pair of column tiles = heads 0-3 | 4-7) are
+// expressed per column tile and do not change.  The attention part makes one pass per sub-head `sh`, one after the
+// other over the same staged tiles and into the same accumulators: operands contracted over features (q, dO as row
+// operands) are zeroed in the lane groups of the other head (g >> 1 != sh), operands whose lane is an output column (the
+// K, Q, dO B operands) in the other head's columns (lq >> 3 != sh) - so dq / dk / dv of both heads land in their own
+// columns of the one tile, and delta is head-local because dO already is.  A compile-time flag.
+template <class T, int NT, bool SPLIT, bool LOOP, bool TWO>
 __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, ColsumPlan sums, int main_grid) {
   // Workgroups beyond main_grid reduce column sums (feta_colsum.h): the LAST launch of a stack's backward runs one workgroup
   // per graph - half the chip at the BASELINE batch - while every split-K partial of the layers behind it, and of this
@@ -83,7 +95,8 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
   typedef Lp<T> L;
   typedef typename L::Op Op;
   typedef typename L::Vec Vec;
-  constexpr int D = kBbD, DH = kBbDH, H = kBbH, P = kBbD + L::PAD, NR = 16 * NT, PEP = NR + 1;
+  constexpr int NS = TWO ? 2 : 1;   // heads of a 16-column tile
+  constexpr int D = kBbD, DH = kBbDH, H = kBbH * NS, P = kBbD + L::PAD, NR = 16 * NT, PEP = NR + 1;
   constexpr int VEC = L::VEC, RV = D / VEC;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, lq = lane & 15, g = lane >> 4;
   // pair of heads of this workgroup: workgroups b and b + B share a graph - and, workgroups being dealt round-robin to
@@ -238,9 +251,14 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
       pev[i] = (idx < NR * NR && qq < a.N && kk < a.N) ? v : 0.0f;
     }
     {
-      const int hh = tid / (NR * 2), rem = tid - hh * NR * 2;   // H * NR * 2 <= 512
+      const int hh = tid / (NR * 2), rem = tid - hh * NR * 2;   // 4 heads: H * NR * 2 <= 512
       const float sv = a.attn_stats[(((int64_t)b * H + min(hh, H - 1)) * a.N + min(rem >> 1, nm1)) * 2 + (rem & 1)];
       if (tid < H * NR * 2) ST[tid] = sv;
+      if constexpr (TWO) {   // 8 heads: up to 1024 values
+        const int idx = tid + kBbThreads, h2 = idx / (NR * 2), rem2 = idx - h2 * NR * 2;
+        const float sv2 = a.attn_stats[(((int64_t)b * H + min(h2, H - 1)) * a.N + min(rem2 >> 1, nm1)) * 2 + (rem2 & 1)];
+        if (idx < H * NR * 2) ST[idx] = sv2;
+      }
       if (tid < NR) RS[tid] = (a.rowscale != nullptr && tid < a.N) ? a.rowscale[grow(tid)] : (tid < a.N ? 1.0f : 0.0f);
     }
     // db_out = column sums of (degree g1): taken here from the fp32 values, BEFORE g1 is rounded into its tile (behind a
@@ -413,6 +431,8 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
       r0[t] = zero4();
       r1[t] = zero4();
     }
+    // (the 4-head form is kept as it was, textually: its instantiations compile to what they were)
+    if constexpr (!TWO) {
     if (role == 0) {
       Op kf[NT], vf[NT], kb[NT];
 #pragma unroll
@@ -502,6 +522,117 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
           r0[kt] = L::mma(L::mk(ds[0], ds[1], ds[2], ds[3]), qb4[qb], r0[kt]);    // dk
         }
       }
+    }
+    } else {
+    auto attn_head = [&](auto shc) __attribute__((always_inline)) {
+    constexpr int sh = decltype(shc)::value;
+    // (LOOP: the lane id is laundered per head as it is per graph - what the second pass derives from it is recomputed
+    // there, not held across the first)
+    int lane_h = lane;
+    if (LOOP) FETA_OPAQUE_LANE(lane_h);
+    const int lq = lane_h & 15, g = lane_h >> 4;
+    const bool ga = (g >> 1) == sh, la = (lq >> 3) == sh;   // this head's features / columns
+    const int hs = NS * h + sh;                                             // the head: its softmax statistics
+    auto mg = [&](const Op& x) __attribute__((always_inline)) { return L::sel(ga, x, L::zero()); };
+    auto ml = [&](const Op& x) __attribute__((always_inline)) { return L::sel(la, x, L::zero()); };
+    if (role == 0) {
+      Op kf[NT], vf[NT], kb[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int rowl = 16 * t + lq;
+        kf[t] = L::ld(Ks + rowl * P + co + 4 * g);
+        vf[t] = L::ld(Vs + rowl * P + co + 4 * g);
+        kb[t] = ml(L::gather(Ks + (16 * t + 4 * g) * P + co + lq, P));
+      }
+#pragma unroll
+      for (int qb = 0; qb < NT; ++qb) {
+        const int q = 16 * qb + lq;
+        const Op qf = mg(L::ld_scaled(Qs + q * P + co + 4 * g, a.scale));   // (rows >= N of the tiles are zero)
+        const Op dof = mg(L::ld(Ds + q * P + co + 4 * g));
+        const Op of = L::ld(Os + q * P + co + 4 * g);
+        float delta = L::get(dof, 0) * L::get(of, 0) + L::get(dof, 1) * L::get(of, 1) + L::get(dof, 2) * L::get(of, 2) +
+                      L::get(dof, 3) * L::get(of, 3);
+        delta += shfl_xor(delta, 16);
+        delta += shfl_xor(delta, 32);
+        const float m = ST[(hs * NR + q) * 2], z = ST[(hs * NR + q) * 2 + 1];
+        const float rinv = fast_rcp(fmaxf(z, 1e-6f));   // (v_rcp_f32, 1 ulp: a full-precision division is a dozen instructions)
+        if (z < 1e-6f) delta = 0.0f;
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt) {
+          if (16 * kt >= n) continue;
+          if (SPLIT && ((qb * NT + kt) & 1) != half) continue;   // the partner wave takes the other tile pairs
+          const f32x4 s = L::mma(kf[kt], qf, zero4());
+          const f32x4 da = L::mma(vf[kt], dof, zero4());
+          float pd[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = 16 * kt + 4 * g + r;
+            const float p = key < n ? fast_exp(s[r] - m) * PE[q * PEP + key] * rinv : 0.0f;
+            pd[r] = p * (da[r] - delta);
+          }
+          r0[qb] = L::mma(L::mk(pd[0], pd[1], pd[2], pd[3]), kb[kt], r0[qb]);  // (query 4g+r, c lq)
+        }
+      }
+    } else {
+      Op qf[NT], dof[NT], qb4[NT], dob[NT];
+      float sd[NT][4], mq[NT][4], rz[NT][4];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int rowl = 16 * t + lq;
+        qf[t] = mg(L::ld_scaled(Qs + rowl * P + co + 4 * g, a.scale));
+        dof[t] = mg(L::ld(Ds + rowl * P + co + 4 * g));
+        const T* colq = Qs + (16 * t + 4 * g) * P + co + lq;
+        const T* cold = Ds + (16 * t + 4 * g) * P + co + lq;
+        const T* colo = Os + (16 * t + 4 * g) * P + co + lq;
+        float qv4[4], dv4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int rr = 16 * t + 4 * g + r;
+          const bool ok = rr < a.N;
+          dv4[r] = L::ld1(cold + r * P);
+          qv4[r] = L::ld1(colq + r * P) * a.scale;
+          if (!la) dv4[r] = qv4[r] = 0.0f;   // (a select: the other head's columns)
+          sd[t][r] = row16_sum(dv4[r] * L::ld1(colo + r * P));   // delta[q = 4g + r]
+          // softmax statistics of the query: once per query, not once per (query, key tile) - the division alone is
+          // a dozen instructions and this role is the one the other waves wait for
+          const float z = ST[(hs * NR + rr) * 2 + 1];
+          mq[t][r] = ST[(hs * NR + rr) * 2];
+          rz[t][r] = ok ? fast_rcp(fmaxf(z, 1e-6f)) : 0.0f;
+          if (z < 1e-6f) sd[t][r] = 0.0f;
+        }
+        qb4[t] = L::mk(qv4[0], qv4[1], qv4[2], qv4[3]);
+        dob[t] = L::mk(dv4[0], dv4[1], dv4[2], dv4[3]);
+      }
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt) {
+        if (16 * kt >= n) continue;
+        const int key = 16 * kt + lq;
+        const Op kf = L::ld(Ks + key * P + co + 4 * g);   // (rows >= n_real of the k / v tiles are zero)
+        const Op vf = L::ld(Vs + key * P + co + 4 * g);
+#pragma unroll
+        for (int qb = 0; qb < NT; ++qb) {
+          if (SPLIT && ((kt * NT + qb) & 1) != half) continue;
+          // (LOOP: the graph loop leaves no registers to hold these two row operands of every query tile - 32 at four
+          // tiles: they are read where they are used)
+          const Op qfq = LOOP ? mg(L::ld_scaled(Qs + (16 * qb + lq) * P + co + 4 * g, a.scale)) : qf[qb];
+          const Op dfq = LOOP ? mg(L::ld(Ds + (16 * qb + lq) * P + co + 4 * g)) : dof[qb];
+          const f32x4 s = L::mma(qfq, kf, zero4());
+          const f32x4 da = L::mma(dfq, vf, zero4());
+          float pp[4], ds[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int q = 16 * qb + 4 * g + r;
+            pp[r] = key < n ? fast_exp(s[r] - mq[qb][r]) * PE[q * PEP + key] * rz[qb][r] : 0.0f;   // rz = 0: q >= N
+            ds[r] = pp[r] * (da[r] - sd[qb][r]);
+          }
+          r1[kt] = L::mma(L::mk(pp[0], pp[1], pp[2], pp[3]), dob[qb], r1[kt]);    // dv (key 4g+r, c lq)
+          r0[kt] = L::mma(L::mk(ds[0], ds[1], ds[2], ds[3]), qb4[qb], r0[kt]);    // dk
+        }
+      }
+    }
+    };  // one head of the column tile
+    attn_head(std::integral_constant<int, 0>{});
+    attn_head(std::integral_constant<int, 1>{});
     }
     // fp32 column sums of this wave's dq | dk, dv accumulators (rows beyond the real / padded length are zero): the
     // bias gradient of in_proj, before the accumulators are rounded into the tiles
@@ -715,25 +846,25 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
   FETA_RT_LAUNCH_DONE(feta_bbwd_launch);
 }
 
-template <class T, int NT>
+template <class T, int NT, bool TWO = false>
 int launch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
-  size_t lds = block_bwd_lds_bytes<T>(NT, a.bn1 != nullptr, a.ln1_gamma != nullptr);
+  size_t lds = block_bwd_lds_bytes<T>(NT, a.bn1 != nullptr, a.ln1_gamma != nullptr, TWO ? 2 * kBbH : kBbH);
   const int grid = feta_attn_block_bwd_blocks(a.B);
   ColsumPlan plan{};
   const int tiles = plan_colsum(segs, nseg, plan);
   if (tiles > 0 && lds < sizeof(float) * colsum_role_lds_floats(kBbThreads)) lds = sizeof(float) * colsum_role_lds_floats(kBbThreads);
   if (a.dx_b != nullptr) {   // two workgroups per graph
-    auto kern = attn_block_bwd_kernel<T, NT, true, false>;
+    auto kern = attn_block_bwd_kernel<T, NT, true, false, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
     hipLaunchKernelGGL(kern, dim3(2 * a.B + tiles), dim3(kBbThreads), lds, stream, a, plan, 2 * a.B);
   } else if (grid == a.B) {
-    auto kern = attn_block_bwd_kernel<T, NT, false, false>;
+    auto kern = attn_block_bwd_kernel<T, NT, false, false, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
     hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid);
   } else {
-    auto kern = attn_block_bwd_kernel<T, NT, false, true>;
+    auto kern = attn_block_bwd_kernel<T, NT, false, true, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
     hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid);
@@ -751,6 +882,16 @@ int dispatch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, 
   }
 }
 
+// 8 heads (d_h = 8): fp32 storage only
+static int dispatch_block_bwd_two(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
+  switch ((a.N + 15) / 16) {
+    case 1: return launch_block_bwd<float, 1, true>(a, segs, nseg, stream);
+    case 2: return launch_block_bwd<float, 2, true>(a, segs, nseg, stream);
+    case 3: return launch_block_bwd<float, 3, true>(a, segs, nseg, stream);
+    default: return launch_block_bwd<float, 4, true>(a, segs, nseg, stream);
+  }
+}
+
 }  // namespace feta
 
 using namespace feta;
@@ -762,7 +903,7 @@ extern "C" int feta_debug_bbwd_stamps(unsigned long long* out256) {
 #endif
 
 extern "C" int feta_attn_block_bwd_supported(int N, int d_model, int heads) {
-  return (d_model == kBbD && heads == kBbH && N >= 1 && N <= 64) ? 1 : 0;
+  return (d_model == kBbD && (heads == 4 || heads == 8) && N >= 1 && N <= 64) ? 1 : 0;
 }
 
 /* partial rows of a launch = its workgroups: one per graph up to kBbMaxGrid (FETA_BLOCK_BWD_MAX_GRID: tests force the
@@ -800,6 +941,11 @@ extern "C" int feta_attn_block_bwd_sums(const feta_attn_block_grad* d, const fet
                aligned16(a.y1) && aligned16(a.dout2) && aligned16(a.g_sum) && aligned16(a.dx_b),
                "attn_block_bwd: tensors must be 16-byte aligned");
   FETA_REQUIRE(a.dtype == FETA_F32 || a.dtype == FETA_BF16, "attn_block_bwd: dtype %d", a.dtype);
+  FETA_REQUIRE(a.H == 0 || a.H == 4 || a.H == 8, "attn_block_bwd: H=%d (0 = 4, 4 or 8 heads)", a.H);
+  if (a.H == 8) {
+    FETA_REQUIRE(a.dtype == FETA_F32, "attn_block_bwd: 8 heads need fp32 storage");
+    return dispatch_block_bwd_two(a, segs, nseg, (hipStream_t)stream);
+  }
   if (a.dtype == FETA_BF16) return dispatch_block_bwd<bf16_t>(a, segs, nseg, (hipStream_t)stream);
   return dispatch_block_bwd<float>(a, segs, nseg, (hipStream_t)stream);
 }

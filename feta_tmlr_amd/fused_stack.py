@@ -62,6 +62,8 @@ USE_ATTN_BLOCK_BWD_LOOP = os.environ.get('FETA_BLOCK_BWD_LOOP', '1') != '0'
 def _fused_attn_bwd(abi, b, n, d, heads, tie, dt):
     if not (USE_ATTN_BLOCK_BWD and not tie and abi.attn_block_bwd_supported(n, d, heads)):
         return False
+    if heads != 4 and dt != torch.float32:   # (the 8-head form is fp32 storage only)
+        return False
     gb = abi.attn_block_bwd_blocks(b)
     return gb > 0 and (gb == b or dt != torch.float32 or USE_ATTN_BLOCK_BWD_LOOP)
 
@@ -106,6 +108,8 @@ def lowp_stack_supported(abi, layers, n, b, d_model):
         return False
     l0 = layers[0]
     heads = l0.self_attn.num_heads
+    if heads != 4:   # the 8-head form of the block kernels (ABI 13) is instantiated for fp32 storage only
+        return False
     if l0.self_attn.tie_qk or (not l0.batch_norm and not USE_LN_STACK):
         return False
     if not (abi.attn_block_supported(n, d_model, heads) and abi.attn_block_bwd_supported(n, d_model, heads)
@@ -291,7 +295,7 @@ class FusedEncoderStackFn(torch.autograd.Function):
                 # F1 + F2 + F3 in one launch, one or two workgroups per graph (csrc/block.hip)
                 G1 = abi.attn_block_stat_rows(b, n)
                 st1 = new(G1 + 1, 2, d)      # (+ the shift row: the sums are relative to norm1's running mean)
-                abi.attn_block_fwd(b, n, scale, stream, tie_qk=tie, x=y_prev, w_in=w_in, b_in=b_in, w_out=w_o,
+                abi.attn_block_fwd(b, n, scale, stream, heads=heads, tie_qk=tie, x=y_prev, w_in=w_in, b_in=b_in, w_out=w_o,
                                    b_out=b_o, pe=pe_c, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
                                    attn_stats=ast, attn=attn, y=y1, y_stats=st1, y_shift=layer.norm1.running_mean,
                                    out_f32=(out32 if li == nl - 1 else None),
@@ -483,7 +487,7 @@ class FusedEncoderStackFn(torch.autograd.Function):
                 dx0b = newt(m, d) if split else None
                 GB = abi.attn_block_bwd_blocks(b)
                 gs_prev = new(2 * GB, 2, d) if li > 0 else None
-                abi.attn_block_bwd(b, n, scale, stream, Gs=G1s, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'],
+                abi.attn_block_bwd(b, n, scale, stream, heads=heads, Gs=G1s, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'],
                                    dx_b=dx0b,
                                    bn1=s['prm1'], g_sum=gs1, fin_out=fin1, dgamma=dg1, dbeta=db1, rowscale=degree_rows,
                                    w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
@@ -606,7 +610,7 @@ class FusedLayerNormStackFn(torch.autograd.Function):
                 out32 = new(n, b, heads, dh)
             y1 = newt(m, d)
             if block:
-                abi.attn_block_fwd(b, n, scale, stream, tie_qk=tie, x=x_in, w_in=w_in, b_in=b_in, w_out=w_o,
+                abi.attn_block_fwd(b, n, scale, stream, heads=heads, tie_qk=tie, x=x_in, w_in=w_in, b_in=b_in, w_out=w_o,
                                    b_out=b_o, pe=pe_c, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
                                    attn_stats=ast, attn=attn, y=y1, y_stats=new(abi.attn_block_stat_rows(b, n) + 1, 2, d),   # (statistics unused)
                                    out_f32=(out32 if li == nl - 1 else None),
@@ -763,7 +767,7 @@ class FusedLayerNormStackFn(torch.autograd.Function):
             if fused_attn:
                 # out_proj + attention + in_proj backward in one launch, one workgroup per graph (csrc/block_bwd.hip)
                 dx0 = newt(m, d)
-                abi.attn_block_bwd(b, n, scale, stream, partial_ptr=ppo, partial_ld=ta, dy=dy1, rowscale=degree_rows,
+                abi.attn_block_bwd(b, n, scale, stream, heads=heads, partial_ptr=ppo, partial_ld=ta, dy=dy1, rowscale=degree_rows,
                                    w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
                                    dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
                                    attn_stats=s['ast'], x0=s['x0'], dx=dx0)
@@ -848,7 +852,7 @@ def _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, 
         if lowp and li == nl - 1:
             out32 = new(n, b, heads, dh)
         y1 = newt(m, d)
-        abi.attn_block_fwd(b, n, scale, stream, x=x_pre, w_in=w_in, b_in=b_in, w_out=w_o, b_out=b_o, pe=pe_c, n_real=n_real,
+        abi.attn_block_fwd(b, n, scale, stream, heads=heads, x=x_pre, w_in=w_in, b_in=b_in, w_out=w_o, b_out=b_o, pe=pe_c, n_real=n_real,
                            rowscale=degree_rows, qkv=qkv, out=out, attn_stats=ast, attn=attn, y=y1, y_stats=None,
                            out_f32=(out32 if li == nl - 1 else None),
                            sums=(pending.take_fwd() if (pending is not None and li == 0) else ()), **ln_prev)
@@ -938,7 +942,7 @@ def _ln_on_load_backward(ctx, d_final, d_concat_last):
         ln0 = {}
         if li > 0:
             ln0 = dict(x0_ln_gamma=params[(li - 1) * PER_LAYER + 10], x0_ln_beta=params[(li - 1) * PER_LAYER + 11])
-        abi.attn_block_bwd(b, n, scale, stream, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'], ln1_gamma=g1,
+        abi.attn_block_bwd(b, n, scale, stream, heads=heads, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'], ln1_gamma=g1,
                            ln_eps=eps1, dx_b=dx0b, rowscale=degree_rows, w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
                            dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
                            attn_stats=s['ast'], x0=s['x0'], dx=dx0, **ln0)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FETA_ABI_VERSION 12
+#define FETA_ABI_VERSION 13
 
 #define FETA_OK 0
 #define FETA_E_ARG (-1)     /* bad shape / stride / alignment / unsupported size */
@@ -462,7 +462,7 @@ int feta_bn_bwd(const float* y, const float* dout, const float* mean_rstd, const
                 int M, int D, feta_stream_t stream);
 
 /* ---- attention sub-block of one encoder layer in ONE launch --------------------------------
- * Replaces, for d_model = 64 = 4 heads x 16 and N <= 64 (feta_attn_block_supported), the sequence
+ * Replaces, for d_model = 64 = 4 heads x 16 or (ABI 13, field H) 8 heads x 8 and N <= 64 (feta_attn_block_supported), the sequence
  * feta_rowlin_fwd_ex (in_proj) -> feta_attn_fwd -> feta_rowlin_fwd_ex (out_proj + degree + residual
  * + BatchNorm statistics) of DiffTransformerEncoderLayer.forward (contract
  * transformer/models.py:166-167,179,244; body per upstream GraphiT, README.md:129).
@@ -472,8 +472,8 @@ int feta_bn_bwd(const float* y, const float* dout, const float* mean_rstd, const
  * parameter block) or x_stats [Gx][2][64] fresh partial sums that this launch finalizes
  * (publishing x_bn_out and updating x_rmean / x_rvar), or neither (first layer).
  * Outputs: qkv [M,192] (in_proj result, for backward), out [M,64] (per-head attention outputs,
- * concatenated: out_each_head), attn_stats [B,4,N,2] (row max, un-clamped row sum), attn
- * [B,4,N,N] or NULL, y [M,64] = x_norm + rowscale * (out W_out^T + b_out), y_stats [G][2][64]
+ * concatenated: out_each_head), attn_stats [B,H,N,2] (row max, un-clamped row sum), attn
+ * [B,H,N,N] or NULL, y [M,64] = x_norm + rowscale * (out W_out^T + b_out), y_stats [G][2][64]
  * partial (sum, sum of squares) over the rows of y - padded rows included, as nn.BatchNorm1d over the
  * [N*B, d] view counts them; NULL (ABI 9): no statistics are taken (LayerNorm stack).
  * G = feta_attn_block_stat_rows(B, N) (ABI 8): one row per WORKGROUP - a graph is one
@@ -522,6 +522,9 @@ typedef struct feta_attn_block {
                               written (norm2 of DiffTransformerEncoderLayer with batch_norm=False, the reference's
                               default: experiments/run_transformer_gengcn_cv.py:56).  Excludes x_bn / x_stats. */
   const float* x_ln_beta;  /* [64], with x_ln_gamma */
+  int H;               /* heads (ABI 13): 0 or 4 = 4 heads x 16, 8 = 8 heads x 8 (fp32 storage only; a 16-column tile of
+                          the kernels then holds two heads and attn_stats / attn are [B,8,N,2] / [B,8,N,N]).  The
+                          feta_attn_out_* entry points take 4 heads only. */
 } feta_attn_block;
 
 int feta_attn_block_supported(int N, int d_model, int heads);
@@ -550,7 +553,7 @@ int feta_attn_out_fwd(const feta_attn_block* d, feta_stream_t stream);
 int feta_attn_out_fwd_sums(const feta_attn_block* d, const feta_colsum_seg* segs, int nseg, feta_stream_t stream);
 
 /* ---- backward of the attention sub-block in ONE launch ------------------------------------------------------
- * (feta_attn_block_bwd_supported: d_model = 64, 4 heads, N <= 64; K not tied to Q.)  Replaces
+ * (feta_attn_block_bwd_supported: d_model = 64, 4 heads or - ABI 13, field H - 8 heads, N <= 64; K not tied to Q.)  Replaces
  * feta_rowlin_bwd_ex (out_proj) -> feta_attn_bwd -> feta_rowlin_bwd_ex (in_proj) of the layer's backward:
  *   g1 = BatchNorm-1 backward of dy (y1 [M,64], bn1 [4][64], partial sums g_sum [Gs][2][64] finalized here ->
  *        fin_out [2][64], dgamma, dbeta) - or dy itself when y1 is NULL (LayerNorm stack);
@@ -605,6 +608,8 @@ typedef struct feta_attn_block_grad {
                                beta computed per row on load (feta_attn_block.x_ln_gamma); excludes bn0 */
   const float* x0_ln_beta;
   float ln_eps;
+  int H;             /* heads (ABI 13): 0 or 4 = 4 heads x 16, 8 = 8 heads x 8 (fp32 storage only; attn_stats [B,8,N,2]);
+                        SPLIT keeps its meaning per pair of 16-column tiles: workgroup 0 heads 0-3, workgroup 1 heads 4-7 */
 } feta_attn_block_grad;
 
 int feta_attn_block_bwd_supported(int N, int d_model, int heads);

@@ -46,6 +46,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--n-pad', type=int, default=37)
+    ap.add_argument('--heads', type=int, default=4, choices=[4, 8], help='8: the d_h = 8 form (fp32 storage)')
     ap.add_argument('--kernel', choices=sorted(KERNELS), default='fwd')
     ap.add_argument('--split', action='store_true', help='bwd: the two-workgroups-per-graph form')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='storage type of the token tensors')
@@ -59,7 +60,7 @@ def main():
     lib = ctypes.CDLL(a.lib)
     abi = _abi.bind(lib)
     dev = torch.device('cuda:0')
-    b, n, d, h = a.batch, a.n_pad, 64, 4
+    b, n, d, h = a.batch, a.n_pad, 64, a.heads
     g = torch.Generator().manual_seed(0)
     nr = torch.randint(9, n + 1, (b,), generator=g, dtype=torch.int32).to(dev)
     pe = torch.rand(b, n, n, generator=g).to(dev)
