@@ -279,9 +279,16 @@ class EncoderInfer(C.Structure):
     ]
 
 
+class EncoderInferEx(C.Structure):
+    """struct feta_encoder_infer_ex (include/feta_hip.h) - field order must match the header."""
+    _fields_ = EncoderInfer._fields_ + [('dtype', C.c_int), ('in_dtype', C.c_int)]
+
+
 SIGNATURES.update({
     'feta_encoder_infer_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     'feta_encoder_infer': ([C.POINTER(EncoderInfer), _S], C.c_int),
+    'feta_encoder_infer_ex_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+    'feta_encoder_infer_ex': ([C.POINTER(EncoderInferEx), _S], C.c_int),
 })
 
 ABI_VERSION = 13
@@ -874,10 +881,8 @@ class Abi:
     def encoder_infer_supported(self, n, d_model, heads, ff, nl):
         return bool(self.lib.feta_encoder_infer_supported(n, d_model, heads, ff, nl))
 
-    def encoder_infer(self, b, n, heads, ff, layers, layer_norm, stream, seq_first=True, **ptrs):
-        """feta_encoder_infer (ABI 12): the whole stack's forward for inference in one launch.  layers: one dict per
-        layer - tensors for the pointer fields of feta_encoder_layer, n1_eps / n2_eps / tie_qk as numbers;
-        tensor-valued keyword arguments (x, pe, n_real, rowscale, y, out, attn) become the descriptor's pointers."""
+    @staticmethod
+    def _encoder_table(layers):
         table = (EncoderLayer * len(layers))()
         for e, lp in zip(table, layers):
             for k, v in lp.items():
@@ -886,6 +891,13 @@ class Abi:
                     setattr(e, k, v.data_ptr())
                 elif v is not None:
                     setattr(e, k, v)
+        return table
+
+    def encoder_infer(self, b, n, heads, ff, layers, layer_norm, stream, seq_first=True, **ptrs):
+        """feta_encoder_infer (ABI 12): the whole stack's forward for inference in one launch.  layers: one dict per
+        layer - tensors for the pointer fields of feta_encoder_layer, n1_eps / n2_eps / tie_qk as numbers;
+        tensor-valued keyword arguments (x, pe, n_real, rowscale, y, out, attn) become the descriptor's pointers."""
+        table = self._encoder_table(layers)
         d = EncoderInfer()
         d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
         d.norm = 1 if layer_norm else 0
@@ -896,6 +908,40 @@ class Abi:
                 setattr(d, k, t.data_ptr())
         d.layers = C.cast(table, C.c_void_p)
         self._check(self.lib.feta_encoder_infer(C.byref(d), stream), 'feta_encoder_infer')
+
+    def encoder_infer_ex_supported(self, n, d_model, heads, ff, nl, dtype=torch.float32):
+        return bool(self.lib.feta_encoder_infer_ex_supported(n, d_model, heads, ff, nl, self._dt_of(dtype)))
+
+    @staticmethod
+    def _dt_of(dtype):
+        if dtype == torch.float32:
+            return 0
+        if dtype == torch.bfloat16:
+            return 1
+        raise TypeError('float32 or bfloat16, got %s' % dtype)
+
+    def encoder_infer_ex(self, b, n, heads, ff, layers, layer_norm, stream, dtype=torch.float32, seq_first=True, **ptrs):
+        """feta_encoder_infer_ex: encoder_infer with a tile / compute type `dtype` (torch.float32: the fp32 kernel, bit for
+        bit; torch.bfloat16: bf16 tiles and bf16 MFMAs, 4 heads).  x and pe are float32 or - with dtype bfloat16 -
+        bfloat16 tensors of ONE type (the descriptor's in_dtype); everything else is float32, the outputs included."""
+        table = self._encoder_table(layers)
+        d = EncoderInferEx()
+        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
+        d.norm = 1 if layer_norm else 0
+        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d.dtype = self._dt_of(dtype)
+        x, pe = ptrs.get('x'), ptrs.get('pe')
+        if x is None:
+            raise ValueError('feta_encoder_infer_ex: x is missing')
+        if pe is not None and pe.dtype != x.dtype:
+            raise TypeError('x is %s, pe is %s: one in_dtype for both' % (x.dtype, pe.dtype))
+        d.in_dtype = self._dt_of(x.dtype)
+        _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k not in ('n_real', 'x', 'pe')))
+        for k, t in ptrs.items():
+            if t is not None:
+                setattr(d, k, t.data_ptr())
+        d.layers = C.cast(table, C.c_void_p)
+        self._check(self.lib.feta_encoder_infer_ex(C.byref(d), stream), 'feta_encoder_infer_ex')
 
 
 def bind(cdll):

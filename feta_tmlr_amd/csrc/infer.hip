@@ -15,11 +15,23 @@
 // The work items of a GEMM phase are (column tile, row tile) pairs, dealt in contiguous column-major runs (infer_gemm),
 // of the attention phase (head, query tile) pairs, dealt round-robin to the waves.
 //
+// The kernel is written once against the storage policy of feta_lp.h, T in {float, bf16_t} (feta_encoder_infer_ex):
+//   T = float   the tiles hold fp32 and every contraction is a chain of v_mfma_f32_16x16x4_f32 - feta_encoder_infer;
+//   T = bf16_t  the evaluation of a model on bf16 storage (layers.set_storage_dtype): the tiles hold bf16 (pitch + 8:
+//               53,248 B for 64 rows with pe, three workgroups per CU where fp32 has one), each group of four k-steps
+//               is one v_mfma_f32_16x16x16_bf16, and accumulators, softmax, degree scale, residual adds and both norms
+//               are fp32 - a value is rounded once, when it is written to a tile or becomes an operand.  Weights, biases,
+//               norm parameters and running statistics stay the fp32 master tensors and are rounded in registers when a
+//               wave loads them for its run of tiles (staging a layer's 64 KB of bf16 weights in LDS would cost two of
+//               the three resident workgroups); x and pe arrive as fp32 or bf16 and are rounded while they are staged;
+//               y, out and attn leave as fp32.  d_h = 16 only: bf16 storage has no d_h = 8 form anywhere in the package.
+//
 // Eight waves (512 lanes), two per SIMD: one wave's VALU and LDS work issues under the other's 32-cycle MFMAs, and the
 // phases have 12 NT, H NT, 4 NT and ff / 16 NT work items (NT = 16-row tiles of the graph: at the ZINC shape 36, 12 - 24,
 // 12, 24) - sixteen waves would leave most of them idle in every phase but in_proj, four would put a single wave on a SIMD.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "feta_abi_common.h"
 #include "feta_ln.h"
@@ -27,16 +39,24 @@
 namespace feta {
 
 constexpr int kInfD = 64;
-constexpr int kInfP = kInfD + 4;        // LDS pitch of a 64-float row (16-byte operand reads)
-constexpr int kInfQP = 3 * kInfD + 4;   // ... of a q | k | v row; the hidden rows h (pitch ff + 4) reuse that tile
 constexpr int kInfWaves = 8, kInfThreads = 64 * kInfWaves;
 constexpr int kInfMaxGrid = 512;        // graphs in flight (two workgroups per CU where the LDS allows); beyond that a
                                         // workgroup walks graphs b, b + grid, ...
+constexpr int kInfMaxGridLp = 768;      // ... of the bf16 form: three workgroups per CU (LDS and registers).  Measured at
+                                        // B = 1024, N = 64, 3 layers: 256 / 512 / 768 / 1024 -> 214 / 160 / 143 / 150 us
+
+// LDS pitches in elements of T: a 64-wide row (fp32: 16-byte operand reads, bf16: 8-byte), a q | k | v row - the hidden
+// rows h (pitch ff + PAD) reuse that tile
+template <class T>
+struct InfTile {
+  static constexpr int P = kInfD + Lp<T>::PAD;
+  static constexpr int QP = 3 * kInfD + Lp<T>::PAD;
+};
 
 // Kernel arguments: the layer table travels BY VALUE (no device table, no copy before the launch: capturable as is).
 struct InferArgs {
-  const float* x;
-  const float* pe;
+  const void* x;     // fp32, or bf16 when in_bf16 (bf16 form only)
+  const void* pe;
   const int32_t* n_real;
   const float* rowscale;
   float* y;
@@ -45,35 +65,73 @@ struct InferArgs {
   int64_t row_sb, row_sn;
   int B, N, L, norm;
   float scale;
+  int in_bf16;
   feta_encoder_layer layers[FETA_ENCODER_MAX_LAYERS];
 };
 static_assert(sizeof(InferArgs) <= 4096, "the layer table must fit HIP's 4 KB of kernel arguments");
 
+template <class T>
 __host__ __device__ inline int infer_lds_bytes(int nt, bool pe) {
   const int nr = 16 * nt;
-  return 4 * (2 * nr * kInfP + nr * kInfQP + (pe ? nr * (nr + 4) : 0));
+  return (int)sizeof(T) * (2 * nr * InfTile<T>::P + nr * InfTile<T>::QP + (pe ? nr * (nr + Lp<T>::PAD) : 0));
+}
+
+// Operand of a contraction over K features from a row of an fp32 master weight in global memory, rounded to T in
+// registers (chunk j: features 16 j + 4 g .. + 3, the bijection of feta_tiles.h)
+template <class T, int K>
+__device__ __forceinline__ void infer_load_w(RowOp<T, K>& t, const float* row, int g) {
+#pragma unroll
+  for (int j = 0; j < RowOp<T, K>::NJ; ++j) {
+    const float4 x = *reinterpret_cast<const float4*>(row + 16 * j + 4 * g);
+    t.o[j] = Lp<T>::mk(x.x, x.y, x.z, x.w);
+  }
+}
+
+// The d_h features of one head of a q / k row in the q | k | v tile as ONE operand chunk; d_h = 8 is half a chunk
+// (lanes g >= 2 carry zeros and read nothing)
+template <class T, int DH>
+__device__ __forceinline__ typename Lp<T>::Op infer_head_op(const T* row, int g) {
+  static_assert(DH == 16 || DH == 8, "one operand chunk per head");
+  if (DH == 16 || 4 * g < DH) return Lp<T>::ld(row + 4 * g);
+  return Lp<T>::zero();
+}
+template <class T, int DH>
+__device__ __forceinline__ typename Lp<T>::Op infer_head_op_scaled(const T* row, int g, float scale) {
+  if (DH == 16 || 4 * g < DH) return Lp<T>::ld_scaled(row + 4 * g, scale);
+  return Lp<T>::zero();
+}
+
+// element i of an operand kept where keep[i], zero elsewhere (bf16: on the packed bits, nothing is converted)
+__device__ __forceinline__ Lp<float>::Op infer_keep4(const Lp<float>::Op& o, const bool (&keep)[4]) {
+  return Lp<float>::mk(keep[0] ? o.v[0] : 0.0f, keep[1] ? o.v[1] : 0.0f, keep[2] ? o.v[2] : 0.0f, keep[3] ? o.v[3] : 0.0f);
+}
+__device__ __forceinline__ Lp<bf16_t>::Op infer_keep4(const Lp<bf16_t>::Op& o, const bool (&keep)[4]) {
+  Lp<bf16_t>::Op r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r.v[i] = keep[i] ? o.v[i] : (short)0;
+  return r;
 }
 
 // rows . W^T over K features for all CT x NT output tiles, register r of a tile <-> (output column 16 ct + 4 g + r,
 // row 16 rt + lq); epi(ct, rt, acc) consumes a tile.  Tiles are dealt to the waves in contiguous column-major runs, so a
-// wave's consecutive tiles mostly share a column tile and its weight operand (read from global memory) is loaded once
-// per run, not once per tile.  skip(ct): column tiles nobody needs (wave-uniform).
-template <int K, int CT, int NT, class Skip, class Epi>
-__device__ __forceinline__ void infer_gemm(const float* rows, int pitch, const float* w, int wave, int lq, int g,
+// wave's consecutive tiles mostly share a column tile and its weight operand (read from global memory, rounded to T in
+// registers) is loaded once per run, not once per tile.  skip(ct): column tiles nobody needs (wave-uniform).
+template <class T, int K, int CT, int NT, class Skip, class Epi>
+__device__ __forceinline__ void infer_gemm(const T* rows, int pitch, const float* w, int wave, int lq, int g,
                                            Skip skip, Epi epi) {
   constexpr int total = CT * NT, per = (total + kInfWaves - 1) / kInfWaves;
-  Feat<K> wf;
+  RowOp<T, K> wf;
   int wct = -1;
   for (int t = wave * per; t < (wave + 1) * per && t < total; ++t) {
     const int ct = t / NT, rt = t - ct * NT;
     if (skip(ct)) continue;
     if (ct != wct) {
-      load_row<K>(wf, w + (int64_t)(16 * ct + lq) * K, g);
+      infer_load_w<T, K>(wf, w + (int64_t)(16 * ct + lq) * K, g);
       wct = ct;
     }
-    Feat<K> xf;
-    load_row<K>(xf, rows + (16 * rt + lq) * pitch, g);
-    epi(ct, rt, dot_rows<K>(wf, xf, zero4()));
+    RowOp<T, K> xf;
+    load_row_op<T, K>(xf, rows + (16 * rt + lq) * pitch, g);
+    epi(ct, rt, dot_row_ops<T, K>(wf, xf, zero4()));
   }
 }
 
@@ -82,80 +140,96 @@ __device__ __forceinline__ float4 infer_bias4(const float* b, int c) {
 }
 
 // norm1 / norm2 of every staged row, in place: 16 lanes per row, four columns each (NR * 16 lanes are whole waves, so
-// the DPP row sums of the LayerNorm run in complete waves)
-template <int NR>
-__device__ __forceinline__ void infer_norm_rows(float* Xs, int norm, const float* gamma, const float* beta,
+// the DPP row sums of the LayerNorm run in complete waves); fp32 arithmetic on the tile's values, rounded on the store
+template <class T, int NR>
+__device__ __forceinline__ void infer_norm_rows(T* Xs, int norm, const float* gamma, const float* beta,
                                                 const float* mean, const float* var, float eps) {
   for (int idx = threadIdx.x; idx < NR * 16; idx += kInfThreads) {
     const int c = 4 * (idx & 15);
-    float4* p = reinterpret_cast<float4*>(Xs + (idx >> 4) * kInfP + c);
-    const float4 v = *p;
-    float f[4] = {v.x, v.y, v.z, v.w};
+    T* p = Xs + (idx >> 4) * InfTile<T>::P + c;
+    float f[4];
+    Lp<T>::ld4(p, f);
     if (norm == FETA_NORM_LAYER) {
       ln_apply<4>(f, gamma + c, beta + c, eps);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) f[e] = (f[e] - mean[c + e]) * rsqrtf(var[c + e] + eps) * gamma[c + e] + beta[c + e];
     }
-    *p = make_float4(f[0], f[1], f[2], f[3]);
+    Lp<T>::st4(p, f[0], f[1], f[2], f[3]);
   }
 }
 
-template <int NT, int DH, int FF>
+template <class T, int NT, int DH, int FF>
 __global__ __launch_bounds__(kInfThreads) void encoder_infer_kernel(InferArgs a) {
-  constexpr int NR = 16 * NT, H = kInfD / DH, PEP = NR + 4, HP = FF + 4;
-  static_assert(HP <= kInfQP, "the hidden rows reuse the q | k | v tile");
-  float* Xs = feta_lds;              // [NR][kInfP]  layer input -> y1 -> x1 -> y2 -> next layer's input
-  float* QKV = Xs + NR * kInfP;      // [NR][kInfQP] q | k | v;  h [NR][HP] after the attention phase
-  float* Os = QKV + NR * kInfQP;     // [NR][kInfP]  concatenated heads
-  float* Pe = Os + NR * kInfP;       // [NR][PEP]    pe of the graph (zero outside N x N), when given
-  float* Hs = QKV;
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lq = lane & 15, g = lane >> 4;
+  typedef Lp<T> P;
+  typedef typename Lp<T>::Op Op;
+  constexpr bool kLp = !std::is_same<T, float>::value;
+  static_assert(!kLp || DH == 16, "bf16 storage has no d_h = 8 form");
+  constexpr int NR = 16 * NT, H = kInfD / DH, XP = InfTile<T>::P, QP = InfTile<T>::QP, PEP = NR + P::PAD, HP = FF + P::PAD;
+  static_assert(HP <= QP, "the hidden rows reuse the q | k | v tile");
+  T* Xs = reinterpret_cast<T*>(feta_lds);   // [NR][XP]  layer input -> y1 -> x1 -> y2 -> next layer's input
+  T* QKV = Xs + NR * XP;             // [NR][QP]  q | k | v;  h [NR][HP] after the attention phase
+  T* Os = QKV + NR * QP;             // [NR][XP]  concatenated heads
+  T* Pe = Os + NR * XP;              // [NR][PEP] pe of the graph (zero outside N x N), when given
+  T* Hs = QKV;
+  const int tid = threadIdx.x;
   const bool has_pe = a.pe != nullptr;
+  const bool in_lp = kLp && a.in_bf16 != 0;   // x and pe arrive as bf16 (wave-uniform)
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     const int n = a.n_real[b];
     // ---- the graph's rows (rows >= N: zero, computed like the others and never stored) and its pe block ----
     for (int idx = tid; idx < NR * 16; idx += kInfThreads) {
       const int i = idx >> 4, c = 4 * (idx & 15);
-      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (i < a.N) v = *reinterpret_cast<const float4*>(a.x + ((int64_t)b * a.row_sb + (int64_t)i * a.row_sn) * kInfD + c);
-      *reinterpret_cast<float4*>(Xs + i * kInfP + c) = v;
+      float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (i < a.N) {
+        const int64_t off = ((int64_t)b * a.row_sb + (int64_t)i * a.row_sn) * kInfD + c;
+        if (in_lp) Lp<bf16_t>::ld4(static_cast<const bf16_t*>(a.x) + off, v);
+        else Lp<float>::ld4(static_cast<const float*>(a.x) + off, v);
+      }
+      P::st4(Xs + i * XP + c, v[0], v[1], v[2], v[3]);
     }
     if (has_pe) {
       for (int idx = tid; idx < NR * NR; idx += kInfThreads) {
         const int i = idx / NR, k = idx - i * NR;
-        Pe[i * PEP + k] = (i < a.N && k < a.N) ? a.pe[((int64_t)b * a.N + i) * a.N + k] : 0.0f;
+        float v = 0.0f;
+        if (i < a.N && k < a.N) {
+          const int64_t off = ((int64_t)b * a.N + i) * a.N + k;
+          v = in_lp ? bf2f(static_cast<const bf16_t*>(a.pe)[off]) : static_cast<const float*>(a.pe)[off];
+        }
+        P::st1(Pe + i * PEP + k, v);
       }
     }
     lds_barrier();
     for (int l = 0; l < a.L; ++l) {
       const feta_encoder_layer& p = a.layers[l];
       const bool last = l + 1 == a.L;
+      // bf16 form: what a lane derives from its id is recomputed per layer, not held in registers across the whole
+      // graph loop (the 80 registers of six waves per SIMD hold no such invariants without scratch)
+      int tl = tid;
+      if (kLp) FETA_OPAQUE_LANE(tl);
+      const int w = tl >> 6, lane = tl & 63, lq = lane & 15, g = lane >> 4;
       // ---- 1. in_proj ----
       const bool tie = p.tie_qk != 0;
-      infer_gemm<kInfD, 12, NT>(Xs, kInfP, p.w_in, w, lq, g, [&](int ct) { return tie && ct >= 4 && ct < 8; },  // K is Q
-                                [&](int ct, int rt, f32x4 acc) {
+      infer_gemm<T, kInfD, 12, NT>(Xs, XP, p.w_in, w, lq, g, [&](int ct) { return tie && ct >= 4 && ct < 8; },  // K is Q
+                                   [&](int ct, int rt, f32x4 acc) {
         const float4 bv = infer_bias4(p.b_in, 16 * ct + 4 * g);
-        *reinterpret_cast<float4*>(QKV + (16 * rt + lq) * kInfQP + 16 * ct + 4 * g) =
-            make_float4(acc[0] + bv.x, acc[1] + bv.y, acc[2] + bv.z, acc[3] + bv.w);
+        P::st4(QKV + (16 * rt + lq) * QP + 16 * ct + 4 * g, acc[0] + bv.x, acc[1] + bv.y, acc[2] + bv.z, acc[3] + bv.w);
       });
       lds_barrier();
       // ---- 2. attention: (head h, query tile qb) ----
-      const float* Ks = QKV + (p.tie_qk ? 0 : kInfD);
-      const float* Vs = QKV + 2 * kInfD;
+      const T* Ks = QKV + (p.tie_qk ? 0 : kInfD);
+      const T* Vs = QKV + 2 * kInfD;
       for (int t = w; t < H * NT; t += kInfWaves) {
         const int h = t % H, qb = t / H, q = 16 * qb + lq;
-        Feat<DH> qf;
-        load_row<DH>(qf, QKV + q * kInfQP + DH * h, g, a.scale);
+        const Op qf = infer_head_op_scaled<T, DH>(QKV + q * QP + DH * h, g, a.scale);
         f32x4 s[NT];
         float m = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
           s[kt] = zero4();
           if (16 * kt < n) {   // a key tile without a real node: nothing (wave-uniform)
-            Feat<DH> kf;
-            load_row<DH>(kf, Ks + (16 * kt + lq) * kInfQP + DH * h, g);
-            s[kt] = dot_rows<DH>(kf, qf, zero4());   // (key 16 kt + 4 g + r, query q)
+            const Op kf = infer_head_op<T, DH>(Ks + (16 * kt + lq) * QP + DH * h, g);
+            s[kt] = P::mma(kf, qf, zero4());   // (key 16 kt + 4 g + r, query q)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
               if (16 * kt + 4 * g + r < n) m = fmaxf(m, s[kt][r]);
@@ -167,9 +241,8 @@ __global__ __launch_bounds__(kInfThreads) void encoder_infer_kernel(InferArgs a)
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
           if (16 * kt >= n) continue;
-          float4 pv = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-          if (has_pe) pv = *reinterpret_cast<const float4*>(Pe + q * PEP + 16 * kt + 4 * g);
-          const float pr[4] = {pv.x, pv.y, pv.z, pv.w};
+          float pr[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+          if (has_pe) P::ld4(Pe + q * PEP + 16 * kt + 4 * g, pr);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float e = 16 * kt + 4 * g + r < n ? fast_exp(s[kt][r] - m) * pr[r] : 0.0f;
@@ -186,18 +259,16 @@ __global__ __launch_bounds__(kInfThreads) void encoder_infer_kernel(InferArgs a)
           if (16 * kt >= n) continue;
 #pragma unroll
           for (int r = 0; r < 4; ++r) s[kt][r] *= rinv;
-          // P (query lq, key 16 kt + 4 g + r) as the A operand of step r, V (that key, column lq of the head) as B;
-          // padded keys carry no value, lanes lq >= DH (d_h = 8: half a tile) feed columns nobody stores
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = 16 * kt + 4 * g + r;
-            const float v = (key < n && lq < DH) ? Vs[key * kInfQP + DH * h + lq] : 0.0f;
-            o = mfma16(s[kt][r], v, o);   // (query 16 qb + 4 g + r, column lq)
-          }
+          // P (query lq, keys 16 kt + 4 g + r) as the A operand, V (those keys, column lq of the head) as B; padded
+          // keys carry no value, lanes lq >= DH (d_h = 8: half a tile) feed columns nobody stores
+          const int key = 16 * kt + 4 * g;
+          const bool keep[4] = {key < n && lq < DH, key + 1 < n && lq < DH, key + 2 < n && lq < DH, key + 3 < n && lq < DH};
+          const Op vf = infer_keep4(P::gather(Vs + key * QP + DH * h + (lq < DH ? lq : 0), QP), keep);
+          o = P::mma(P::mk(s[kt]), vf, o);   // (query 16 qb + 4 g + r, column lq)
         }
         if (lq < DH) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) Os[(16 * qb + 4 * g + r) * kInfP + DH * h + lq] = o[r];
+          for (int r = 0; r < 4; ++r) P::st1(Os + (16 * qb + 4 * g + r) * XP + DH * h + lq, o[r]);
         }
         if (last && a.attn != nullptr && q < a.N) {
           float* dst = a.attn + (((int64_t)b * H + h) * a.N + q) * a.N;
@@ -211,93 +282,97 @@ __global__ __launch_bounds__(kInfThreads) void encoder_infer_kernel(InferArgs a)
       lds_barrier();
       // ---- 3. out_proj + bias, * degree, + residual (in place) ----
       const auto none = [](int) { return false; };
-      infer_gemm<kInfD, 4, NT>(Os, kInfP, p.w_out, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
+      infer_gemm<T, kInfD, 4, NT>(Os, XP, p.w_out, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
         const int node = 16 * rt + lq, c0 = 16 * ct + 4 * g;
         const float4 bo = infer_bias4(p.b_out, c0);
         const float rs = (a.rowscale != nullptr && node < a.N)
                              ? a.rowscale[(int64_t)b * a.row_sb + (int64_t)node * a.row_sn] : 1.0f;
-        float4* xr = reinterpret_cast<float4*>(Xs + node * kInfP + c0);
-        const float4 x = *xr;
-        *xr = make_float4((acc[0] + bo.x) * rs + x.x, (acc[1] + bo.y) * rs + x.y, (acc[2] + bo.z) * rs + x.z,
-                          (acc[3] + bo.w) * rs + x.w);
+        T* xr = Xs + node * XP + c0;
+        float x[4];
+        P::ld4(xr, x);
+        P::st4(xr, (acc[0] + bo.x) * rs + x[0], (acc[1] + bo.y) * rs + x[1], (acc[2] + bo.z) * rs + x[2],
+               (acc[3] + bo.w) * rs + x[3]);
       });
       lds_barrier();
       // ---- 4. norm1 ----
-      infer_norm_rows<NR>(Xs, a.norm, p.n1_gamma, p.n1_beta, p.n1_mean, p.n1_var, p.n1_eps);
+      infer_norm_rows<T, NR>(Xs, a.norm, p.n1_gamma, p.n1_beta, p.n1_mean, p.n1_var, p.n1_eps);
       lds_barrier();
       // ---- 5. linear1 + relu -> h; linear2 + bias + residual (in place) ----
-      infer_gemm<kInfD, FF / 16, NT>(Xs, kInfP, p.w1, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
+      infer_gemm<T, kInfD, FF / 16, NT>(Xs, XP, p.w1, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
         const float4 bv = infer_bias4(p.b1, 16 * ct + 4 * g);
-        *reinterpret_cast<float4*>(Hs + (16 * rt + lq) * HP + 16 * ct + 4 * g) =
-            make_float4(fmaxf(acc[0] + bv.x, 0.0f), fmaxf(acc[1] + bv.y, 0.0f), fmaxf(acc[2] + bv.z, 0.0f),
-                        fmaxf(acc[3] + bv.w, 0.0f));
+        P::st4(Hs + (16 * rt + lq) * HP + 16 * ct + 4 * g, fmaxf(acc[0] + bv.x, 0.0f), fmaxf(acc[1] + bv.y, 0.0f),
+               fmaxf(acc[2] + bv.z, 0.0f), fmaxf(acc[3] + bv.w, 0.0f));
       });
       lds_barrier();
-      infer_gemm<FF, 4, NT>(Hs, HP, p.w2, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
+      infer_gemm<T, FF, 4, NT>(Hs, HP, p.w2, w, lq, g, none, [&](int ct, int rt, f32x4 acc) {
         const int c0 = 16 * ct + 4 * g;
         const float4 bv = infer_bias4(p.b2, c0);
-        float4* xr = reinterpret_cast<float4*>(Xs + (16 * rt + lq) * kInfP + c0);
-        const float4 x = *xr;
-        *xr = make_float4(x.x + (acc[0] + bv.x), x.y + (acc[1] + bv.y), x.z + (acc[2] + bv.z), x.w + (acc[3] + bv.w));
+        T* xr = Xs + (16 * rt + lq) * XP + c0;
+        float x[4];
+        P::ld4(xr, x);
+        P::st4(xr, x[0] + (acc[0] + bv.x), x[1] + (acc[1] + bv.y), x[2] + (acc[2] + bv.z), x[3] + (acc[3] + bv.w));
       });
       lds_barrier();
       // ---- 6. norm2 ----
-      infer_norm_rows<NR>(Xs, a.norm, p.n2_gamma, p.n2_beta, p.n2_mean, p.n2_var, p.n2_eps);
+      infer_norm_rows<T, NR>(Xs, a.norm, p.n2_gamma, p.n2_beta, p.n2_mean, p.n2_var, p.n2_eps);
       lds_barrier();
     }
-    // ---- the last layer's output rows and concatenated heads ----
+    // ---- the last layer's output rows and concatenated heads (fp32 whatever T is) ----
     for (int idx = tid; idx < a.N * 16; idx += kInfThreads) {
       const int i = idx >> 4, c = 4 * (idx & 15);
       const int64_t row = (int64_t)b * a.row_sb + (int64_t)i * a.row_sn;
-      *reinterpret_cast<float4*>(a.y + row * kInfD + c) = *reinterpret_cast<const float4*>(Xs + i * kInfP + c);
-      *reinterpret_cast<float4*>(a.out + row * kInfD + c) = *reinterpret_cast<const float4*>(Os + i * kInfP + c);
+      float yv[4], ov[4];
+      P::ld4(Xs + i * XP + c, yv);
+      P::ld4(Os + i * XP + c, ov);
+      *reinterpret_cast<float4*>(a.y + row * kInfD + c) = make_float4(yv[0], yv[1], yv[2], yv[3]);
+      *reinterpret_cast<float4*>(a.out + row * kInfD + c) = make_float4(ov[0], ov[1], ov[2], ov[3]);
     }
     lds_barrier();   // (the next graph's rows overwrite Xs)
   }
 }
 
-template <int NT, int DH, int FF>
-int launch_infer(const InferArgs& a, hipStream_t stream) {
-  const size_t lds = infer_lds_bytes(NT, a.pe != nullptr);
-  auto kern = encoder_infer_kernel<NT, DH, FF>;
+template <class T, int NT, int DH, int FF>
+int launch_infer(const InferArgs& a, hipStream_t stream, const char* what) {
+  const size_t lds = infer_lds_bytes<T>(NT, a.pe != nullptr);
+  auto kern = encoder_infer_kernel<T, NT, DH, FF>;
   static LdsSeen lds_seen;
   allow_dynamic_lds(kern, lds, lds_seen);
-  int cap = kInfMaxGrid;   // FETA_INFER_MAX_GRID: tests force the walking loop
+  int cap = std::is_same<T, float>::value ? kInfMaxGrid : kInfMaxGridLp;   // FETA_INFER_MAX_GRID: tests force the walking loop
   if (const char* e = getenv("FETA_INFER_MAX_GRID")) cap = atoi(e) > 0 ? atoi(e) : cap;
   const int grid = a.B < cap ? a.B : cap;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kInfThreads), lds, stream, a);
-  return check_launch("feta_encoder_infer");
+  return check_launch(what);
 }
 
-template <int NT, int DH>
-int launch_infer_ff(const InferArgs& a, int ff, hipStream_t stream) {
-  return ff == 64 ? launch_infer<NT, DH, 64>(a, stream) : launch_infer<NT, DH, 128>(a, stream);
+template <class T, int NT, int DH>
+int launch_infer_ff(const InferArgs& a, int ff, hipStream_t stream, const char* what) {
+  return ff == 64 ? launch_infer<T, NT, DH, 64>(a, stream, what) : launch_infer<T, NT, DH, 128>(a, stream, what);
 }
 
 template <int NT>
-int launch_infer_heads(const InferArgs& a, int heads, int ff, hipStream_t stream) {
-  return heads == 4 ? launch_infer_ff<NT, 16>(a, ff, stream) : launch_infer_ff<NT, 8>(a, ff, stream);
+int launch_infer_heads(const InferArgs& a, int dtype, int heads, int ff, hipStream_t stream, const char* what) {
+  if (dtype == FETA_BF16) return launch_infer_ff<bf16_t, NT, 16>(a, ff, stream, what);
+  return heads == 4 ? launch_infer_ff<float, NT, 16>(a, ff, stream, what) : launch_infer_ff<float, NT, 8>(a, ff, stream, what);
 }
 
-}  // namespace feta
-
-using namespace feta;
-
-extern "C" int feta_encoder_infer_supported(int N, int d_model, int heads, int ff, int L) {
-  return (d_model == kInfD && (heads == 4 || heads == 8) && N >= 1 && N <= 64 && (ff == 64 || ff == 128) && L >= 1 &&
-          L <= FETA_ENCODER_MAX_LAYERS) ? 1 : 0;
-}
-
-extern "C" int feta_encoder_infer(const struct feta_encoder_infer* d, feta_stream_t stream) {
-  FETA_REQUIRE(d != nullptr, "encoder_infer: null descriptor");
-  FETA_REQUIRE(feta_encoder_infer_supported(d->N, kInfD, d->H, d->FF, d->L),
-               "encoder_infer: N=%d H=%d ff=%d L=%d outside 1 <= N <= 64, H in {4, 8}, ff in {64, 128}, 1 <= L <= %d",
-               d->N, d->H, d->FF, d->L, FETA_ENCODER_MAX_LAYERS);
-  FETA_REQUIRE(d->B > 0, "encoder_infer: B=%d", d->B);
-  FETA_REQUIRE(d->norm == FETA_NORM_BATCH || d->norm == FETA_NORM_LAYER, "encoder_infer: norm kind %d", d->norm);
-  FETA_REQUIRE(d->x && d->n_real && d->y && d->out && d->layers, "encoder_infer: null pointer");
-  FETA_REQUIRE(aligned16(d->x) && aligned16(d->y) && aligned16(d->out), "encoder_infer: x, y, out must be 16-byte aligned");
-  FETA_REQUIRE(d->row_sb >= 0 && d->row_sn >= 0, "encoder_infer: negative row strides");
+// both entry points: `what` names the one that was called in every message
+int run_infer(const struct feta_encoder_infer_ex* d, feta_stream_t stream, const char* what) {
+  FETA_REQUIRE(d != nullptr, "%s: null descriptor", what);
+  FETA_REQUIRE(d->dtype == FETA_F32 || d->dtype == FETA_BF16, "%s: dtype %d is neither FETA_F32 nor FETA_BF16", what, d->dtype);
+  FETA_REQUIRE(d->in_dtype == FETA_F32 || d->in_dtype == FETA_BF16, "%s: in_dtype %d is neither FETA_F32 nor FETA_BF16",
+               what, d->in_dtype);
+  FETA_REQUIRE(d->dtype == FETA_F32 || d->H == 4, "%s: H=%d with dtype FETA_BF16 - the bf16 form has 4 heads (d_h = 16) only",
+               what, d->H);
+  FETA_REQUIRE(feta_encoder_infer_ex_supported(d->N, kInfD, d->H, d->FF, d->L, d->dtype),
+               "%s: N=%d H=%d ff=%d L=%d outside 1 <= N <= 64, H in {4, 8}, ff in {64, 128}, 1 <= L <= %d",
+               what, d->N, d->H, d->FF, d->L, FETA_ENCODER_MAX_LAYERS);
+  FETA_REQUIRE(d->dtype == FETA_BF16 || d->in_dtype == FETA_F32, "%s: in_dtype FETA_BF16 needs dtype FETA_BF16 (the fp32 "
+               "form reads fp32 x and pe)", what);
+  FETA_REQUIRE(d->B > 0, "%s: B=%d", what, d->B);
+  FETA_REQUIRE(d->norm == FETA_NORM_BATCH || d->norm == FETA_NORM_LAYER, "%s: norm kind %d", what, d->norm);
+  FETA_REQUIRE(d->x && d->n_real && d->y && d->out && d->layers, "%s: null pointer", what);
+  FETA_REQUIRE(aligned16(d->x) && aligned16(d->y) && aligned16(d->out), "%s: x, y, out must be 16-byte aligned", what);
+  FETA_REQUIRE(d->row_sb >= 0 && d->row_sn >= 0, "%s: negative row strides", what);
   InferArgs a{};
   a.x = d->x;
   a.pe = d->pe;
@@ -313,23 +388,66 @@ extern "C" int feta_encoder_infer(const struct feta_encoder_infer* d, feta_strea
   a.L = d->L;
   a.norm = d->norm;
   a.scale = (float)(1.0 / std::sqrt((double)(kInfD / d->H)));
+  a.in_bf16 = d->in_dtype == FETA_BF16;
   for (int l = 0; l < d->L; ++l) {
     const feta_encoder_layer& p = d->layers[l];
     FETA_REQUIRE(p.w_in && p.w_out && p.w1 && p.w2 && p.n1_gamma && p.n1_beta && p.n2_gamma && p.n2_beta,
-                 "encoder_infer: layer %d: null weight or norm parameter", l);
+                 "%s: layer %d: null weight or norm parameter", what, l);
     FETA_REQUIRE(aligned16(p.w_in) && aligned16(p.b_in) && aligned16(p.w_out) && aligned16(p.b_out) && aligned16(p.w1) &&
                  aligned16(p.b1) && aligned16(p.w2) && aligned16(p.b2),
-                 "encoder_infer: layer %d: weights and biases must be 16-byte aligned", l);
+                 "%s: layer %d: weights and biases must be 16-byte aligned", what, l);
     FETA_REQUIRE(d->norm != FETA_NORM_BATCH || (p.n1_mean && p.n1_var && p.n2_mean && p.n2_var),
-                 "encoder_infer: layer %d: BatchNorm needs running_mean and running_var", l);
-    FETA_REQUIRE(p.n1_eps >= 0.0f && p.n2_eps >= 0.0f, "encoder_infer: layer %d: negative eps", l);
+                 "%s: layer %d: BatchNorm needs running_mean and running_var", what, l);
+    FETA_REQUIRE(p.n1_eps >= 0.0f && p.n2_eps >= 0.0f, "%s: layer %d: negative eps", what, l);
     a.layers[l] = p;
   }
   hipStream_t s = (hipStream_t)stream;
+  const char* name = d->dtype == FETA_BF16 ? "feta_encoder_infer_ex (bf16)" : "feta_encoder_infer";
   switch ((d->N + 15) / 16) {
-    case 1: return launch_infer_heads<1>(a, d->H, d->FF, s);
-    case 2: return launch_infer_heads<2>(a, d->H, d->FF, s);
-    case 3: return launch_infer_heads<3>(a, d->H, d->FF, s);
-    default: return launch_infer_heads<4>(a, d->H, d->FF, s);
+    case 1: return launch_infer_heads<1>(a, d->dtype, d->H, d->FF, s, name);
+    case 2: return launch_infer_heads<2>(a, d->dtype, d->H, d->FF, s, name);
+    case 3: return launch_infer_heads<3>(a, d->dtype, d->H, d->FF, s, name);
+    default: return launch_infer_heads<4>(a, d->dtype, d->H, d->FF, s, name);
   }
+}
+
+}  // namespace feta
+
+using namespace feta;
+
+extern "C" int feta_encoder_infer_supported(int N, int d_model, int heads, int ff, int L) {
+  return (d_model == kInfD && (heads == 4 || heads == 8) && N >= 1 && N <= 64 && (ff == 64 || ff == 128) && L >= 1 &&
+          L <= FETA_ENCODER_MAX_LAYERS) ? 1 : 0;
+}
+
+extern "C" int feta_encoder_infer_ex_supported(int N, int d_model, int heads, int ff, int L, int dtype) {
+  if (dtype == FETA_F32) return feta_encoder_infer_supported(N, d_model, heads, ff, L);
+  return (dtype == FETA_BF16 && heads == 4 && feta_encoder_infer_supported(N, d_model, heads, ff, L)) ? 1 : 0;
+}
+
+extern "C" int feta_encoder_infer(const struct feta_encoder_infer* d, feta_stream_t stream) {
+  FETA_REQUIRE(d != nullptr, "encoder_infer: null descriptor");
+  struct feta_encoder_infer_ex e{};
+  e.x = d->x;
+  e.row_sb = d->row_sb;
+  e.row_sn = d->row_sn;
+  e.pe = d->pe;
+  e.n_real = d->n_real;
+  e.rowscale = d->rowscale;
+  e.y = d->y;
+  e.out = d->out;
+  e.attn = d->attn;
+  e.B = d->B;
+  e.N = d->N;
+  e.H = d->H;
+  e.FF = d->FF;
+  e.L = d->L;
+  e.norm = d->norm;
+  e.layers = d->layers;
+  e.dtype = e.in_dtype = FETA_F32;
+  return run_infer(&e, stream, "encoder_infer");
+}
+
+extern "C" int feta_encoder_infer_ex(const struct feta_encoder_infer_ex* d, feta_stream_t stream) {
+  return run_infer(d, stream, "encoder_infer_ex");
 }

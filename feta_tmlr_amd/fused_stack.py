@@ -1006,20 +1006,23 @@ def fused_encoder_stack(src, pe, degree_rows, n_real, layers, need_attn=True, ta
 
 
 def infer_supported(layers, n, d):
-    """The whole stack runs as ONE feta_encoder_infer launch (inference, ABI 12): one norm kind for every layer (BatchNorm
-    in eval mode with running statistics, or affine LayerNorm), no active dropout, exp(s - rowmax), fp32 storage, and
-    the shapes the kernel covers (d_model = 64, 4 or 8 heads, N <= 64, ff 64 or 128, up to 16 layers)."""
+    """The whole stack runs as ONE launch (inference: feta_encoder_infer, ABI 12, for fp32 storage and
+    feta_encoder_infer_ex for bf16 storage): one norm kind for every layer (BatchNorm in eval mode with running
+    statistics, or affine LayerNorm), no active dropout, exp(s - rowmax), one storage type for every layer, and the
+    shapes the kernel covers (d_model = 64, 4 or 8 heads - bf16 storage: 4 -, N <= 64, ff 64 or 128, up to 16 layers)."""
     if not len(layers):
         return False
     l0 = layers[0]
-    bn, heads, ff = l0.batch_norm, l0.self_attn.num_heads, l0.linear1.out_features
+    bn, heads, ff, dt = l0.batch_norm, l0.self_attn.num_heads, l0.linear1.out_features, l0.storage_dtype
+    if dt not in (torch.float32, torch.bfloat16):
+        return False
     for l in layers:
         a = l.self_attn
         if l.batch_norm != bn or a.num_heads != heads or l.linear1.out_features != ff:
             return False
         if l.training and (l.dropout1.p > 0.0 or l.dropout.p > 0.0 or l.dropout2.p > 0.0 or a.dropout > 0.0):
             return False
-        if getattr(a, 'stab', 'rowmax') != 'rowmax' or l.storage_dtype != torch.float32:
+        if getattr(a, 'stab', 'rowmax') != 'rowmax' or l.storage_dtype != dt:
             return False
         for nm in (l.norm1, l.norm2):
             if bn:
@@ -1030,20 +1033,24 @@ def infer_supported(layers, n, d):
                   or tuple(nm.normalized_shape) != (d,)):
                 return False
     abi = _lib._TEST_ABI if _lib._TEST_ABI is not None else _lib.abi()
-    return abi.encoder_infer_supported(n, d, heads, ff, len(layers))
+    if dt == torch.float32:
+        return abi.encoder_infer_supported(n, d, heads, ff, len(layers))
+    return abi.encoder_infer_ex_supported(n, d, heads, ff, len(layers), dt)
 
 
 def encoder_stack_infer(src, pe, degree_rows, n_real, layers, need_attn=True):
     """-> (output [N,B,d] of the last layer, concat heads of the last layer [N,B,d], attn [B,H,N,N] or None), as
-    fused_encoder_stack, in ONE launch (feta_encoder_infer): forward only - nothing is saved for a backward pass and the
-    outputs carry no autograd history.  The caller checks infer_supported."""
+    fused_encoder_stack, in ONE launch (feta_encoder_infer; bf16 storage: feta_encoder_infer_ex with bf16 tiles, src and
+    pe fp32 or bf16 as they arrive, fp32 outputs): forward only - nothing is saved for a backward pass and the outputs
+    carry no autograd history.  The caller checks infer_supported."""
     n, b, d = src.shape
     abi, stream = _lib.backend(src)
     l0 = layers[0]
     heads, ff, bn = l0.self_attn.num_heads, l0.linear1.out_features, l0.batch_norm
     x = src.detach().contiguous()
-    y, concat = torch.empty_like(x), torch.empty_like(x)
-    attn = torch.empty(b, heads, n, n, dtype=x.dtype, device=x.device) if need_attn else None
+    y = torch.empty(n, b, d, dtype=torch.float32, device=x.device)
+    concat = torch.empty_like(y)
+    attn = torch.empty(b, heads, n, n, dtype=torch.float32, device=x.device) if need_attn else None
     t = lambda p: None if p is None else p.detach().contiguous()
     table = []
     for l in layers:
@@ -1056,6 +1063,11 @@ def encoder_stack_infer(src, pe, degree_rows, n_real, layers, need_attn=True):
             n2_gamma=t(l.norm2.weight), n2_beta=t(l.norm2.bias),
             n2_mean=t(l.norm2.running_mean) if bn else None, n2_var=t(l.norm2.running_var) if bn else None,
             n1_eps=l.norm1.eps, n2_eps=l.norm2.eps, tie_qk=int(a.tie_qk)))
-    abi.encoder_infer(b, n, heads, ff, table, not bn, stream, x=x, pe=t(pe), n_real=n_real.contiguous(),
-                      rowscale=t(degree_rows), y=y, out=concat, attn=attn)
+    ptrs = dict(x=x, pe=t(pe), n_real=n_real.contiguous(), rowscale=t(degree_rows), y=y, out=concat, attn=attn)
+    if l0.storage_dtype == torch.float32:
+        abi.encoder_infer(b, n, heads, ff, table, not bn, stream, **ptrs)
+    else:
+        if ptrs['pe'] is not None and ptrs['pe'].dtype != x.dtype:    # one in_dtype for both
+            ptrs['pe'] = ptrs['pe'].to(x.dtype)
+        abi.encoder_infer_ex(b, n, heads, ff, table, not bn, stream, dtype=l0.storage_dtype, **ptrs)
     return y, concat, attn

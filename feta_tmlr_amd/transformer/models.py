@@ -225,14 +225,17 @@ class DiffTransformerEncoderGenGCN(nn.Module):
             if degree_rows is None or degree_rows.shape[0] != degree.numel():
                 degree_rows = degree.transpose(0, 1).reshape(-1).contiguous()
         lowp = self.storage_dtype != torch.float32
-        if lowp:
-            if self.filter_mode != 'spectral' or self.learn_only_filter_order_coeff:
-                raise NotImplementedError("the bf16 storage path runs filter_mode='spectral' with matrix coefficients")
+        if lowp and (self.filter_mode != 'spectral' or self.learn_only_filter_order_coeff):
+            raise NotImplementedError("the bf16 storage path runs filter_mode='spectral' with matrix coefficients")
+        # inference (torch.inference_mode): the whole stack as ONE forward-only launch where the shape allows; on bf16
+        # storage the launch rounds the fp32 rows and pe itself while it stages them (no cast launches in front of it)
+        # and hands fp32 tensors to the filter stage, as the fused bf16 training stack does
+        infer = (torch.is_inference_mode_enabled() and self.fused_stack and self.last_layer_filter
+                 and mask is None and output.dtype == torch.float32 and (pe is None or pe.dtype == torch.float32)
+                 and self.layers[0].storage_dtype == self.storage_dtype and infer_supported(self.layers, n, src.shape[-1]))
+        if lowp and not infer:
             output = output.to(self.storage_dtype)
             pe = None if pe is None else pe.to(self.storage_dtype)    # once for all layers
-        # inference (torch.inference_mode): the whole stack as ONE forward-only launch where the shape allows
-        infer = (torch.is_inference_mode_enabled() and not lowp and self.fused_stack and self.last_layer_filter
-                 and mask is None and output.dtype == torch.float32 and infer_supported(self.layers, n, src.shape[-1]))
         fused = (not infer and self.fused_stack and self.last_layer_filter and mask is None
                  and stack_supported(self.layers, src.shape[-1]))
         if lowp and fused:
@@ -242,7 +245,7 @@ class DiffTransformerEncoderGenGCN(nn.Module):
             from .. import _lib
             from ..fused_stack import lowp_stack_supported
             fused = lowp_stack_supported(_lib.backend(output)[0], self.layers, n, src.shape[1], src.shape[-1])
-        lowp = lowp and not fused      # from here on: the op-by-op bf16 path
+        lowp = lowp and not fused and not infer     # from here on: the op-by-op bf16 path
         # BatchNorm stack whose only consumer is linear_cat: the last BatchNorm is applied inside linear_cat's kernels
         tail = None
         if (fused and self.layers[0].batch_norm and self.use_skip_conn and self.norm is None

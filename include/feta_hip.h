@@ -787,6 +787,37 @@ struct feta_encoder_infer {   /* (a struct tag only: the entry point has the sam
 int feta_encoder_infer_supported(int N, int d_model, int heads, int ff, int L);
 int feta_encoder_infer(const struct feta_encoder_infer* d, feta_stream_t stream);
 
+/* ... with a compute type (additive, like feta_rowlin_ex / feta_layernorm_*_ex): the evaluation of a model on bf16
+ * storage in the same ONE launch.
+ *   dtype = FETA_F32   exactly feta_encoder_infer (4 and 8 heads), bit for bit; in_dtype must be FETA_F32.
+ *   dtype = FETA_BF16  the LDS tiles (layer rows, q | k | v, h, concatenated heads, pe) hold bf16 and every contraction
+ *                      is v_mfma_f32_16x16x16_bf16; accumulators, softmax, degree scale, residual adds and both norms are
+ *                      fp32, a value is rounded once, when it is written to a tile or becomes an operand.  Weights, biases,
+ *                      norm parameters and running statistics are the fp32 master tensors (rounded as operands); y, out
+ *                      and attn are fp32, as feta_ffn.y_f32 / feta_attn_block.out_f32 of the training stack.  4 heads
+ *                      (d_h = 16) only: bf16 storage has no d_h = 8 form.
+ *   in_dtype           type of x and pe in HBM (FETA_BF16 with dtype = FETA_BF16 only; x 16-byte aligned either way):
+ *                      they are rounded while they are staged, no cast launch in front of the stack.
+ * feta_encoder_infer_ex_supported: feta_encoder_infer_supported, and heads = 4 for FETA_BF16. */
+struct feta_encoder_infer_ex {   /* (a struct tag only: the entry point has the same name) */
+  const void* x;          /* [M,64] input of the first layer, in_dtype */
+  int64_t row_sb, row_sn;
+  const void* pe;         /* [B,N,N] or NULL, in_dtype */
+  const int32_t* n_real;  /* [B] */
+  const float* rowscale;  /* [M] or NULL */
+  float* y;               /* [M,64] */
+  float* out;             /* [M,64] */
+  float* attn;            /* [B,H,N,N] or NULL */
+  int B, N, H, FF, L;
+  int norm;               /* FETA_NORM_BATCH | FETA_NORM_LAYER */
+  const feta_encoder_layer* layers;  /* HOST pointer to L layer structs */
+  int dtype;              /* FETA_F32 | FETA_BF16: tile / compute type */
+  int in_dtype;           /* FETA_F32 | FETA_BF16: type of x and pe */
+};
+
+int feta_encoder_infer_ex_supported(int N, int d_model, int heads, int ff, int L, int dtype);
+int feta_encoder_infer_ex(const struct feta_encoder_infer_ex* d, feta_stream_t stream);
+
 /* ---- graph preprocessing -------------------------------------------------------------
  * Dense Lhat = -D^-1/2 A D^-1/2 per graph from the batched edge list, with the exact
  * edge-list semantics of ChebConvDynamic.__norm__ (transformer/ChebNetDynamic.py:108-130):

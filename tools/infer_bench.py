@@ -1,6 +1,8 @@
 """Eval forward per batch, eager: torch.no_grad() (the layer-by-layer / fused-training-kernel path) against
 torch.inference_mode() (the encoder stack as ONE feta_encoder_infer launch) at config 2, the reference's ZINC default
 (8 heads, 10 layers, BatchNorm), MUTAG with LayerNorm and the molhiv bucket (B = 1024, N = 64, BatchNorm and LayerNorm).
+--dtype bf16: the same shapes on bf16 storage (layers.set_storage_dtype; inference_mode is then ONE
+feta_encoder_infer_ex launch with bf16 tiles); the 8-head shape is skipped, bf16 storage has no d_h = 8 form.
 Prints one JSON line per shape.  Under `rocprofv3 --kernel-trace --stats -- python tools/infer_bench.py --train` the
 kernel statistics also hold the training forward of config 2 (attn_block_fwd8 + ffn_fwd per layer) for comparison."""
 import argparse
@@ -14,6 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from feta_tmlr_amd.transformer import data as D                     # noqa: E402
+from feta_tmlr_amd.transformer.layers import set_storage_dtype     # noqa: E402
 from feta_tmlr_amd.transformer.models import DiffGraphTransformerGenGCN   # noqa: E402
 
 SHAPES = {   # name: (dataset shape, B, N_pad, heads, layers, batch_norm)
@@ -28,6 +31,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--steps', type=int, default=50)
 ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--shapes', default=','.join(SHAPES))
+ap.add_argument('--dtype', choices=('f32', 'bf16'), default='f32', help='storage type of the model')
 ap.add_argument('--train', action='store_true', help='also run training forward + backward steps at config 2')
 args = ap.parse_args()
 dev = torch.device('cuda:0')
@@ -38,6 +42,8 @@ def build(shape, bsz, n_pad, heads, layers, batch_norm):
     model = DiffGraphTransformerGenGCN(28, 1, 64, heads, dim_feedforward=128, dropout=0.0, nb_layers=layers,
                                        batch_norm=batch_norm, filter_order=4, heads_share_graph=True,
                                        filter_mode='spectral').to(dev)
+    if args.dtype == 'bf16':
+        set_storage_dtype(model, torch.bfloat16)
     ds = D.SyntheticGraphDataset(shape, bsz, in_dim=28, seed=0, n_max=n_pad)
     batch9, cache = D.collate(ds.samples, k_eig=16, n_pad=n_pad, device=dev)
     return model, batch9, cache
@@ -56,6 +62,10 @@ def timed(fn):
 
 for name in args.shapes.split(','):
     shape, bsz, n_pad, heads, layers, bn = SHAPES[name]
+    if args.dtype == 'bf16' and heads != 4:
+        print(json.dumps({'shape': name, 'skipped': 'bf16 storage has no %d-head (d_h = %d) form' % (heads, 64 // heads)}),
+              flush=True)
+        continue
     model, batch9, cache = build(shape, bsz, n_pad, heads, layers, bn)
     x, mask, pe, _, degree, _, edge_index, batch, fi = batch9
     fwd = lambda: model(x, edge_index, batch, fi, mask, pe, degree=degree, graph_cache=cache)
@@ -66,7 +76,7 @@ for name in args.shapes.split(','):
             out.sum().backward()
         timed(step)
     model.eval()
-    res = {'shape': name, 'B': bsz, 'N': n_pad, 'heads': heads, 'layers': layers,
+    res = {'shape': name, 'dtype': args.dtype, 'B': bsz, 'N': n_pad, 'heads': heads, 'layers': layers,
            'norm': 'batch' if bn else 'layer'}
     with torch.no_grad():
         res['no_grad_ms'] = 1e3 * timed(fwd)
