@@ -284,7 +284,19 @@ class EncoderInferEx(C.Structure):
     _fields_ = EncoderInfer._fields_ + [('dtype', C.c_int), ('in_dtype', C.c_int)]
 
 
+class EncoderFwdSave(C.Structure):
+    """struct feta_encoder_fwd_save (include/feta_hip.h) - field order must match the header."""
+    _fields_ = EncoderInferEx._fields_ + [
+        ('qkv', _F), ('out_save', _F), ('attn_stats', _F), ('y1', _F), ('h', _F), ('y2', _F), ('y2_last_f32', _F),
+        ('qkv_stride', C.c_int64), ('out_stride', C.c_int64), ('attn_stats_stride', C.c_int64), ('y1_stride', C.c_int64),
+        ('h_stride', C.c_int64), ('y2_stride', C.c_int64),
+    ]
+
+
 SIGNATURES.update({
+    'feta_encoder_fwd_save_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+    'feta_encoder_fwd_save': ([C.POINTER(EncoderFwdSave), _S], C.c_int),
+    'feta_encoder_fwd_save_sums': ([C.POINTER(EncoderFwdSave), C.POINTER(ColsumSeg), C.c_int, _S], C.c_int),
     'feta_encoder_infer_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     'feta_encoder_infer': ([C.POINTER(EncoderInfer), _S], C.c_int),
     'feta_encoder_infer_ex_supported': ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
@@ -942,6 +954,43 @@ class Abi:
                 setattr(d, k, t.data_ptr())
         d.layers = C.cast(table, C.c_void_p)
         self._check(self.lib.feta_encoder_infer_ex(C.byref(d), stream), 'feta_encoder_infer_ex')
+
+    def encoder_fwd_save_supported(self, n, d_model, heads, ff, nl, dtype=torch.float32, tie_qk=False):
+        return bool(self.lib.feta_encoder_fwd_save_supported(n, d_model, heads, ff, nl, self._dt_of(dtype), int(bool(tie_qk))))
+
+    SAVE_KINDS = ('qkv', 'out_save', 'attn_stats', 'y1', 'h', 'y2')
+
+    def encoder_fwd_save(self, b, n, heads, ff, layers, stream, dtype=torch.float32, seq_first=True, layer_norm=True,
+                         sums=(), **ptrs):
+        """feta_encoder_fwd_save(_sums): the forward of a training step of a LayerNorm stack in one launch.  layers: as
+        encoder_infer.  Keyword tensors: x, pe (storage type `dtype`), n_real, rowscale, y, out, attn, y2_last_f32 and
+        the saved tensors qkv, out_save, attn_stats, y1, h, y2, each [L, ...] (contiguous per layer: the layer stride is
+        the tensor's stride(0)) or, L = 1, without the leading axis.  sums: [(in [R, C], out [C])] column sums that
+        ride in trailing workgroups of the launch."""
+        table = self._encoder_table(layers)
+        d = EncoderFwdSave()
+        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
+        d.norm = 1 if layer_norm else 0
+        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d.dtype = d.in_dtype = self._dt_of(dtype)
+        tok = ('x', 'pe', 'qkv', 'out_save', 'y1', 'h', 'y2')
+        _same_dtype(dtype, *(ptrs.get(k) for k in tok))
+        _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k not in tok + ('n_real',)))
+        for k, t in ptrs.items():
+            if t is not None:
+                setattr(d, k, t.data_ptr())
+        for k in self.SAVE_KINDS:
+            t = ptrs.get(k)
+            if t is not None and len(layers) > 1:
+                if t.shape[0] != len(layers) or not t[0].is_contiguous():
+                    raise ValueError('feta_encoder_fwd_save: %s must be [L, ...] with contiguous layers' % k)
+                setattr(d, k + '_stride' if k != 'out_save' else 'out_stride', t.stride(0))
+        d.layers = C.cast(table, C.c_void_p)
+        if sums:
+            self._check(self.lib.feta_encoder_fwd_save_sums(C.byref(d), self._colsum_segs(sums), len(sums), stream),
+                        'feta_encoder_fwd_save_sums')
+        else:
+            self._check(self.lib.feta_encoder_fwd_save(C.byref(d), stream), 'feta_encoder_fwd_save')
 
 
 def bind(cdll):

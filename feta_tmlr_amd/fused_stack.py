@@ -86,6 +86,32 @@ USE_LN_STACK = os.environ.get('FETA_LN_STACK', '1') != '0'   # 0: LayerNorm laye
 # loads of feta_ffn_bwd / feta_attn_block_bwd) - two launches per layer and direction like the BatchNorm stack, no
 # normalised tensor in HBM; 0: feta_layernorm_fwd / _bwd launches between the fused kernels (round-3 form, A/B timing)
 USE_LN_ON_LOAD = os.environ.get('FETA_LN_ON_LOAD', '1') != '0'
+# LayerNorm stacks on load: the FORWARD of the whole stack as ONE launch (feta_encoder_fwd_save: the kernel of
+# feta_encoder_infer_ex with the stores a backward pass needs) instead of two launches per layer; the backward is
+# unchanged.  Opt-in: '1' here, or one_launch_forward = True on the encoder (layers.set_one_launch_forward)
+USE_LN_ONE_LAUNCH = os.environ.get('FETA_LN_ONE_LAUNCH', '0') != '0'
+
+
+class StackLayers(list):
+    """the layers of one fused_encoder_stack call, with the encoder's one_launch_forward (None: USE_LN_ONE_LAUNCH)"""
+    one_launch = None
+
+
+def ln_one_launch_supported(abi, layers, n, b, d_model, tie, dt):
+    """a LayerNorm-on-load stack whose forward feta_encoder_fwd_save takes: one feed-forward width, head count and eps
+    source for every layer, affine LayerNorms with a bias, and the shapes of the kernel (d_model = 64, N <= 64, ff 64 or
+    128, 4 or - fp32 storage - 8 heads, up to 16 layers, no tie_qk).  Dropout and BatchNorm never get here
+    (stack_supported / ln_on_load_supported)."""
+    if tie or not len(layers) or dt not in (torch.float32, torch.bfloat16):
+        return False
+    l0 = layers[0]
+    heads, ff = l0.self_attn.num_heads, l0.linear1.out_features
+    for l in layers:
+        if l.self_attn.num_heads != heads or l.linear1.out_features != ff or l.self_attn.tie_qk:
+            return False
+        if l.norm1.bias is None or l.norm2.bias is None:
+            return False
+    return abi.encoder_fwd_save_supported(n, d_model, heads, ff, len(layers), dt, tie)
 
 
 def ln_on_load_supported(abi, layers, n, b, d_model, tie):
@@ -574,6 +600,11 @@ class FusedLayerNormStackFn(torch.autograd.Function):
         ctx.on_load = (len(layers) > 0 and ln_on_load_supported(abi, layers, src.shape[0], src.shape[1], src.shape[2],
                                                                  layers[0].self_attn.tie_qk))
         if ctx.on_load:
+            one = getattr(layers, 'one_launch', None)
+            if ((USE_LN_ONE_LAUNCH if one is None else one)
+                    and ln_one_launch_supported(abi, layers, src.shape[0], src.shape[1], src.shape[2],
+                                                layers[0].self_attn.tie_qk, src.dtype)):
+                return _ln_one_launch_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params)
             return _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params)
         if len(layers):
             STACK_FLAT_GRAD.pop(layers[0], None)
@@ -889,6 +920,67 @@ def _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, 
     return final.view(n, b, d), concat_last, attn
 
 
+def _ln_one_launch_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params):
+    """_ln_on_load_forward as ONE launch (feta_encoder_fwd_save): every layer of a graph runs in one workgroup with the
+    activations in LDS, and each layer writes what _ln_on_load_backward reads - qkv, out, the softmax statistics, y1, h,
+    y2 - in the layouts and storage type of feta_attn_block_fwd / feta_ffn_fwd.  The saved tensors are views of one
+    [L, ...] allocation per kind; x0 of layer l > 0 is y2 of layer l - 1.  The pending forward column sums ride in trailing
+    workgroups of the launch; the coefficient generator's forward does not (it reads the attention matrix this launch
+    writes): pending.coeff_fwd_req stays and FilterCoefficientsFn.forward runs its own launch."""
+    if len(layers):
+        STACK_FLAT_GRAD.pop(layers[0], None)
+    n, b, d = src.shape
+    m = n * b
+    nl = len(layers)
+    heads = layers[0].self_attn.num_heads
+    dh = d // heads
+    scale = float(dh) ** -0.5
+    dev = src.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    dt = src.dtype
+    lowp = dt != torch.float32
+    newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
+    if lowp and (pe is not None and pe.dtype != dt):
+        raise TypeError('bf16 stack: pe must be %s as well' % dt)
+    ff = params[6].shape[0]
+    x_pre = src.contiguous().view(m, d)      # layer 0's x0: the tensor the backward reads
+    pe_c = None if pe is None else pe.contiguous()
+    attn = new(b, heads, n, n) if need_attn else None
+    qkv, out, ast = newt(nl, m, 3 * d), newt(nl, n, b, heads, dh), new(nl, b, heads, n, 2)
+    y1, h, y2 = newt(nl, m, d), newt(nl, m, ff), newt(nl, m, d)
+    y2_last = new(m, d) if lowp else y2[nl - 1]      # (what leaves the stack is fp32 whatever the storage type)
+    out32 = new(n, b, heads, dh) if lowp else None
+    final = new(m, d)
+    table = []
+    for li, layer in enumerate(layers):
+        (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
+        t = lambda p: None if p is None else p.detach()
+        table.append(dict(w_in=t(w_in), b_in=t(b_in), w_out=t(w_o), b_out=t(b_o), n1_gamma=t(g1), n1_beta=t(be1),
+                          w1=t(w1), b1=t(bb1), w2=t(w2), b2=t(bb2), n2_gamma=t(g2), n2_beta=t(be2),
+                          n1_eps=float(layer.norm1.eps), n2_eps=float(layer.norm2.eps), tie_qk=0))
+    abi.encoder_fwd_save(b, n, heads, ff, table, stream, dtype=dt, x=x_pre, pe=pe_c, n_real=n_real, rowscale=degree_rows,
+                         y=final, out=out32, attn=attn, qkv=qkv, out_save=out, attn_stats=ast, y1=y1, h=h, y2=y2,
+                         y2_last_f32=(y2_last if lowp else None),
+                         sums=(pending.take_fwd() if pending is not None else ()))
+    saved = []
+    for li in range(nl):
+        saved.append(dict(x0=x_pre, qkv=qkv[li], out=out[li], ast=ast[li], y1=y1[li], h=h[li],
+                          y2=(y2_last if li == nl - 1 else y2[li])))
+        x_pre = saved[-1]['y2']
+    ctx.saved_state = saved
+    if CAPTURE_SAVED is not None:
+        CAPTURE_SAVED.append(saved)
+    ctx.meta = (n, b, d, heads, dh, False, scale, nl)
+    ctx.aux = (pe_c, degree_rows, n_real)
+    ctx.params = params
+    ctx.eps = [(float(l.norm1.eps), float(l.norm2.eps)) for l in layers]
+    ctx.owner = layers[0] if len(layers) else None
+    if attn is not None:
+        ctx.mark_non_differentiable(attn)
+    concat_last = (out32 if lowp else saved[-1]['out']).view(n, b, d)
+    return final.view(n, b, d), concat_last, attn
+
+
 def _ln_on_load_backward(ctx, d_final, d_concat_last):
     saved, params = ctx.saved_state, ctx.params
     n, b, d, heads, dh, tie, scale, nl = ctx.meta
@@ -991,18 +1083,22 @@ def _take_pending(ctx):
     return pend.take()
 
 
-def fused_encoder_stack(src, pe, degree_rows, n_real, layers, need_attn=True, tail=None, pending=None):
+def fused_encoder_stack(src, pe, degree_rows, n_real, layers, need_attn=True, tail=None, pending=None, one_launch=None):
     """-> (output [N,B,d] of the last layer, concat heads of the last layer [N,B,d], attn or None).
     tail (a StackTail, BatchNorm stacks only): the output is the PRE-norm y2 of the last layer and the tail's
     consumer applies the last BatchNorm (functional.row_linear_cat_bn).
     pending (a functional.PendingSums whose stack_armed the caller set): the stack's one reduction launch also
-    carries the column sums the filter stage's backward left in it."""
+    carries the column sums the filter stage's backward left in it.
+    one_launch (LayerNorm stacks): True / False - the forward as one launch where ln_one_launch_supported says so; None:
+    USE_LN_ONE_LAUNCH."""
     params = []
     for l in layers:
         params += layer_params(l)
     bn = layers[0].batch_norm
     fn = FusedEncoderStackFn if bn else FusedLayerNormStackFn
-    return fn.apply(src, pe, degree_rows, n_real, list(layers), need_attn, tail if bn else None, pending, *params)
+    stack = StackLayers(layers)
+    stack.one_launch = one_launch
+    return fn.apply(src, pe, degree_rows, n_real, stack, need_attn, tail if bn else None, pending, *params)
 
 
 def infer_supported(layers, n, d):

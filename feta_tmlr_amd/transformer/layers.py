@@ -227,6 +227,17 @@ def set_storage_dtype(module, dtype):
     return module
 
 
+def set_one_launch_forward(module, flag):
+    """LayerNorm encoders below `module`: run the forward of the layer stack of a TRAINING step as one launch
+    (feta_encoder_fwd_save) where fused_stack.ln_one_launch_supported takes it - True / False, or None to follow
+    fused_stack.USE_LN_ONE_LAUNCH (FETA_LN_ONE_LAUNCH).  Other stacks are unaffected."""
+    assert flag in (None, True, False)
+    for mod in module.modules():
+        if hasattr(mod, 'one_launch_forward'):
+            mod.one_launch_forward = flag
+    return module
+
+
 def clone_layers(layer, n):
     """nn.TransformerEncoder semantics: n deep copies (identical initial weights)."""
     return nn.ModuleList([copy.deepcopy(layer) for _ in range(n)])

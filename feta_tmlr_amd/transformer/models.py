@@ -99,6 +99,9 @@ class DiffTransformerEncoderGenGCN(nn.Module):
         self.storage_dtype = torch.float32   # torch.bfloat16: bf16 storage path (layers.set_storage_dtype)
         self.spectral_k = None    # eigenpairs kept when the eigenbasis is computed here (None: all N_pad)
         self.fused_stack = True   # layer stacks (BatchNorm or LayerNorm) run as one autograd node when the dims allow
+        # LayerNorm stacks: the forward of the whole stack as one launch (fused_stack._ln_one_launch_forward); None: the
+        # module flag fused_stack.USE_LN_ONE_LAUNCH (FETA_LN_ONE_LAUNCH, off by default) - layers.set_one_launch_forward
+        self.one_launch_forward = None
         self.keep_stack_boundary = False   # set by trainers that use backward_head / backward_stack
         self._stack_boundary = None
         self._stack_grads = None
@@ -276,7 +279,8 @@ class DiffTransformerEncoderGenGCN(nn.Module):
                                                                need_attn=True)
                 else:
                     output, concat, attn = fused_encoder_stack(output, pe, degree_rows, cache.n_real,
-                                                               self.layers, need_attn=True, tail=tail, pending=pending)
+                                                               self.layers, need_attn=True, tail=tail, pending=pending,
+                                                               one_launch=self.one_launch_forward)
                     if self.keep_stack_boundary:   # for backward_head / backward_stack
                         self._stack_boundary = (output, concat)
                     elif pending is not None and concat.requires_grad:

@@ -818,6 +818,56 @@ struct feta_encoder_infer_ex {   /* (a struct tag only: the entry point has the 
 int feta_encoder_infer_ex_supported(int N, int d_model, int heads, int ff, int L, int dtype);
 int feta_encoder_infer_ex(const struct feta_encoder_infer_ex* d, feta_stream_t stream);
 
+/* ---- the same stack as the FORWARD OF A TRAINING STEP of a LayerNorm stack, in ONE launch (additive) --------------------
+ * LayerNorm is row-local and attention is per graph, so nothing couples two graphs in training mode either: the kernel
+ * of feta_encoder_infer_ex runs every layer of a graph in one workgroup and - its compile-time SAVE form - every layer l
+ * also writes what the backward kernels (feta_ffn_bwd, feta_attn_block_bwd with the LayerNorm on load) read, in the
+ * layouts, row addressing row(b, i) = b*row_sb + i*row_sn and storage type [T] (dtype) that feta_attn_block_fwd /
+ * feta_ffn_fwd produce:
+ *   qkv        [M,192] [T]   in_proj result incl. bias, unscaled
+ *   out_save   [M,64]  [T]   concatenated heads
+ *   attn_stats [B,H,N,2]     row max of the scaled, masked scores; row sum after * pe, before the 1e-6 clamp
+ *   y1         [M,64]  [T]   rows before norm1
+ *   h          [M,FF]  [T]   after relu
+ *   y2         [M,64]  [T]   rows before norm2 (layer l + 1 reads them as its x0; layer 0's x0 is x itself)
+ * Each is ONE base pointer, layer l at base + l * <kind>_stride ELEMENTS (a multiple of 8; > 0 when L > 1).  Rows i < N
+ * are written, padded rows n_real <= i < N included (computed like every other row, as the training kernels do; k and v
+ * of a key tile without a real node are written too).  bf16 storage: a saved value is the LDS tile's value - what the
+ * forward itself went on to use; the last layer's y2 leaves as fp32 in y2_last_f32 (as feta_ffn.y_f32: y2[L-1] is not
+ * written) and `out` is the fp32 copy of the last layer's concatenated heads (as feta_attn_block.out_f32).  fp32 storage:
+ * `out` may be NULL (out_save + (L-1) * out_stride already is that tensor), y2_last_f32 is not read.
+ * LayerNorm only (norm = FETA_NORM_LAYER), no tie_qk, in_dtype = dtype (x is layer 0's saved x0).  y (after norm2 of the
+ * last layer) and attn leave as in feta_encoder_infer_ex.  _sums: up to FETA_COLSUM_MAX_SEGS pending column sums in
+ * trailing workgroups, as feta_attn_block_fwd_sums.  Capturable: layer table, pointers and strides travel by value. */
+struct feta_encoder_fwd_save {   /* (a struct tag only: the entry point has the same name) */
+  const void* x;          /* [M,64] [T] input of the first layer */
+  int64_t row_sb, row_sn;
+  const void* pe;         /* [B,N,N] [T] or NULL */
+  const int32_t* n_real;  /* [B] */
+  const float* rowscale;  /* [M] or NULL */
+  float* y;               /* [M,64] */
+  float* out;             /* [M,64] fp32 concatenated heads of the last layer (fp32 storage: nullable) */
+  float* attn;            /* [B,H,N,N] or NULL */
+  int B, N, H, FF, L;
+  int norm;               /* FETA_NORM_LAYER */
+  const feta_encoder_layer* layers;  /* HOST pointer to L layer structs */
+  int dtype;              /* FETA_F32 | FETA_BF16: tile / compute / storage type */
+  int in_dtype;           /* = dtype */
+  void* qkv;
+  void* out_save;
+  float* attn_stats;
+  void* y1;
+  void* h;
+  void* y2;
+  float* y2_last_f32;     /* [M,64] (FETA_BF16), else NULL */
+  int64_t qkv_stride, out_stride, attn_stats_stride, y1_stride, h_stride, y2_stride;
+};
+
+int feta_encoder_fwd_save_supported(int N, int d_model, int heads, int ff, int L, int dtype, int tie_qk);
+int feta_encoder_fwd_save(const struct feta_encoder_fwd_save* d, feta_stream_t stream);
+int feta_encoder_fwd_save_sums(const struct feta_encoder_fwd_save* d, const feta_colsum_seg* segs, int nseg,
+                               feta_stream_t stream);
+
 /* ---- graph preprocessing -------------------------------------------------------------
  * Dense Lhat = -D^-1/2 A D^-1/2 per graph from the batched edge list, with the exact
  * edge-list semantics of ChebConvDynamic.__norm__ (transformer/ChebNetDynamic.py:108-130):
