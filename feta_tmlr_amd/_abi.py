@@ -25,6 +25,9 @@ SIGNATURES = {
                       C.c_int),
     'feta_coeff_fwd': ([_F, _I, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _S], C.c_int),
     'feta_coeff_bwd_groups': ([C.c_int, C.c_int], C.c_int),
+    'feta_coeff_dsum': ([_F, _I, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _S], C.c_int),
+    'feta_coeff_bwd_saved_groups': ([C.c_int, C.c_int], C.c_int),
+    'feta_coeff_bwd_saved': ([_F, _F, _F, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _S], C.c_int),
     'feta_coeff_bwd': ([_F, _I, _F, _F, _F, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _S],
                        C.c_int),
     'feta_colsum': ([_F, _F, C.c_int, C.c_int, _S], C.c_int),
@@ -150,7 +153,17 @@ class SpecCatGrad(C.Structure):
     ]
 
 
+class CoeffDsumRole(C.Structure):
+    """struct feta_coeff_dsum_role (include/feta_hip.h)."""
+    _fields_ = [('cj', _F), ('n_real', _I), ('s', _F), ('gcn_bias', _F), ('A', _F), ('Bm', _F),
+                ('B', C.c_int), ('N', C.c_int), ('H', C.c_int), ('C', C.c_int)]
+
+
 SIGNATURES.update({
+    'feta_spec_cat_fwd_coeff_fits': ([C.c_int] * 4, C.c_int),
+    'feta_spec_filter_cat_fwd_coeff': ([_F, C.c_int64, C.c_int64, _F, _F, _F, _F, _I, _F, C.c_int64, C.c_int64,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SpecCat),
+                                        C.POINTER(CoeffDsumRole), _S], C.c_int),
     'feta_spec_cat_bwd_supported': ([C.c_int] * 6, C.c_int),
     'feta_spec_cat_bwd_rows': ([C.c_int], C.c_int),
     'feta_spec_filter_cat_bwd': ([_F, C.c_int64, C.c_int64, _F, _F, _F, _I, C.c_int64, C.c_int64, _F, _F, _F,
@@ -199,6 +212,24 @@ class CoeffBwdRole(C.Structure):
     """struct feta_coeff_bwd_role (include/feta_hip.h)."""
     _fields_ = [('cj', _F), ('n_real', _I), ('s', _F), ('gcn_bias', _F), ('dpooled', _F), ('partial', _F),
                 ('B', C.c_int), ('N', C.c_int), ('H', C.c_int), ('C', C.c_int)]
+
+
+class CoeffSavedReq:
+    """The saved form of the coefficient generator's backward, left by its autograd node for a launch to carry
+    (functional.PendingSums.coeff_bwd_req): dpooled, A, Bm [H*B, C], partial [coeff_bwd_saved_groups, 2, C]."""
+    __slots__ = ('dpooled', 'A', 'Bm', 'partial', 'b', 'h')
+
+    def __init__(self, dpooled, A, Bm, partial, b, h):
+        self.dpooled, self.A, self.Bm, self.partial, self.b, self.h = dpooled, A, Bm, partial, b, h
+
+    def run(self, abi, stream):
+        """on its own launch (nobody carried it): the partials only, the caller reduces them"""
+        abi.coeff_bwd_saved(self.dpooled, self.A, self.Bm, self.partial, None, None, self.b, self.h, stream)
+
+
+class CoeffBwdSavedRole(C.Structure):
+    """struct feta_coeff_bwd_saved_role (include/feta_hip.h)."""
+    _fields_ = [('dpooled', _F), ('A', _F), ('Bm', _F), ('partial', _F), ('B', C.c_int), ('H', C.c_int), ('C', C.c_int)]
 
 
 class Ffn(C.Structure):
@@ -257,6 +288,7 @@ SIGNATURES.update({
     'feta_ffn_bwd_chunks': ([C.c_int, C.c_int], C.c_int),
     'feta_ffn_bwd': ([C.POINTER(FfnGrad), _S], C.c_int),
     'feta_ffn_bwd_coeff': ([C.POINTER(FfnGrad), C.POINTER(CoeffBwdRole), _S], C.c_int),
+    'feta_ffn_bwd_coeff_saved': ([C.POINTER(FfnGrad), C.POINTER(CoeffBwdSavedRole), _S], C.c_int),
 })
 
 class EncoderLayer(C.Structure):
@@ -482,6 +514,19 @@ class Abi:
                                             0 if dw_dense is None else dw_dense.shape[0], b, n, h, c, stream),
                     'feta_coeff_bwd')
 
+    def coeff_dsum(self, cj, n_real, s, gcn_bias, A, Bm, b, n, h, stream):
+        """feta_coeff_dsum: the tanh pass of the backward, from forward data -> A, Bm [H*B, C]"""
+        self._check(self.lib.feta_coeff_dsum(_p(cj), _p(n_real), _p(s), _p(gcn_bias), _p(A), _p(Bm), b, n, h, s.shape[0],
+                                             stream), 'feta_coeff_dsum')
+
+    def coeff_bwd_saved_groups(self, b, h):
+        return self.lib.feta_coeff_bwd_saved_groups(b, h)
+
+    def coeff_bwd_saved(self, dpooled, A, Bm, partial, ds, dbias, b, h, stream, dw_dense=None):
+        self._check(self.lib.feta_coeff_bwd_saved(_p(dpooled), _p(A), _p(Bm), _p(partial), _p(ds), _p(dbias), _p(dw_dense),
+                                                  0 if dw_dense is None else dw_dense.shape[0], b, h, dpooled.shape[1], stream),
+                    'feta_coeff_bwd_saved')
+
     @staticmethod
     def _colsum_segs(pairs):
         """pairs: [(in [R, C] (row stride >= C), out [C]) or (in, out, bcast [rows, C])] -> feta_colsum_seg array"""
@@ -552,11 +597,16 @@ class Abi:
     def spec_cat_supported(self, n, h, dh, order, k, share):
         return bool(self.lib.feta_spec_cat_supported(n, h, dh, order, k, int(share)))
 
+    def spec_cat_fwd_coeff_fits(self, b, n, k, blocks):
+        """can the filter launch of b graphs carry coeff_dsum of `blocks` blocks (dsum= of spec_filter_cat_fwd)"""
+        return bool(self.lib.feta_spec_cat_fwd_coeff_fits(b, n, k, blocks))
+
     def spec_filter_cat_fwd(self, x, u, lam, coeff, bias, n_real, y, order, share, stream, y2, w_cat, b_cat, out,
                             y2_bn=None, y2_stats=None, Gx=0, gamma=None, beta=None, bn_out=None, rmean=None, rvar=None,
-                            nbt=None, momentum=0.1, eps=1e-5):
+                            nbt=None, momentum=0.1, eps=1e-5, dsum=None):
         """feta_spec_filter_cat_fwd: the eigenbasis filter with linear_cat folded in.  y2 [N, B, 64] (or [B, N, 64]
-        batch-first like x) = the stack output, out like y."""
+        batch-first like x) = the stack output, out like y.  dsum (optional): (cj, n_real, s, gcn_bias, A, Bm, b, n, h),
+        the arguments of coeff_dsum - it rides in trailing workgroups (feta_spec_filter_cat_fwd_coeff)."""
         b, n, h, dh = x.shape
         k = u.shape[2]
         xsb, xsn = tok_strides(x)
@@ -570,6 +620,15 @@ class Abi:
                         ('b_cat', b_cat), ('out', out)):
             if t is not None:
                 setattr(c, name, t.data_ptr())
+        if dsum is not None:
+            r = CoeffDsumRole()
+            r.cj, r.n_real, r.s, r.gcn_bias, r.A, r.Bm = (None if t is None else t.data_ptr() for t in dsum[:6])
+            r.B, r.N, r.H, r.C = dsum[6], dsum[7], dsum[8], dsum[2].shape[0]
+            self._check(self.lib.feta_spec_filter_cat_fwd_coeff(_p(x), xsb, xsn, _p(u), _p(lam), _p(coeff), _p(bias),
+                                                                _p(n_real), _p(y), ysb, ysn, b, n, h, dh, order, k, int(share),
+                                                                C.byref(c), C.byref(r), stream),
+                        'feta_spec_filter_cat_fwd_coeff')
+            return
         self._check(self.lib.feta_spec_filter_cat_fwd(_p(x), xsb, xsn, _p(u), _p(lam), _p(coeff), _p(bias), _p(n_real), _p(y),
                                                       ysb, ysn, b, n, h, dh, order, k, int(share), C.byref(c), stream),
                     'feta_spec_filter_cat_fwd')
@@ -811,6 +870,12 @@ class Abi:
     def ffn_bwd_launch(self, desc, stream, coeff=None):
         if coeff is None:
             self._check(self.lib.feta_ffn_bwd(C.byref(desc), stream), 'feta_ffn_bwd')
+            return
+        if isinstance(coeff, CoeffSavedReq):
+            r = CoeffBwdSavedRole()
+            r.dpooled, r.A, r.Bm, r.partial = (t.data_ptr() for t in (coeff.dpooled, coeff.A, coeff.Bm, coeff.partial))
+            r.B, r.H, r.C = coeff.b, coeff.h, coeff.A.shape[1]
+            self._check(self.lib.feta_ffn_bwd_coeff_saved(C.byref(desc), C.byref(r), stream), 'feta_ffn_bwd_coeff_saved')
             return
         cj, n_real, s, gcn_bias, dpooled, partial, b, n, h = coeff
         r = CoeffBwdRole()

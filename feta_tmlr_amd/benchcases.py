@@ -118,9 +118,17 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
         cgen = 4 * (d // heads) ** 2
         cgrp = abi.coeff_bwd_groups(b, heads)
         brole = (rnd(heads * b, n), n_real, rnd(cgen), rnd(cgen), rnd(heads * b, cgen), new(cgrp, 2, cgen), b, n, heads)
+        cbytes = b * (heads * cgen + heads * n) + cgrp * 2 * cgen
+        from . import functional as _F
+        if _F.USE_COEFF_DSUM and n <= 64 and heads * b <= _F.COEFF_ROLE_MAX_BLOCKS:
+            # ... in its saved form where the step takes it (the tanh pass rode in the filter stage's forward launch:
+            # feta_ffn_bwd_coeff_saved - a multiply-and-column-sum in trailing workgroups); the case keeps its name
+            cgrp = abi.coeff_bwd_saved_groups(b, heads)
+            brole = _F.CoeffSavedReq(rnd(heads * b, cgen), rnd(heads * b, cgen), rnd(heads * b, cgen), new(cgrp, 2, cgen),
+                                     b, heads)
+            cbytes = 3 * b * heads * cgen + cgrp * 2 * cgen
         cases.append(('ffn_bwd (+ coefficient generator)', 1.0, lambda: (abi.ffn_bwd_launch(fdsc, st, brole), keep_f)[0],
-                      ft * (4 * m * d + m * ff) + f4 * (2 * d * ff + RCF * cols + b * (heads * cgen + heads * n) + cgrp * 2 * cgen),
-                      ['ffn_bwd']))
+                      ft * (4 * m * d + m * ff) + f4 * (2 * d * ff + RCF * cols + cbytes), ['ffn_bwd']))
         if fused_a:
             # ... below a layer whose attention backward ran as two workgroups per graph: the gradient in two parts
             # (its BatchNorm sums come from that launch: two partial rows per graph)

@@ -46,6 +46,20 @@ __global__ __launch_bounds__(kCoeffThreads) void coeff_bwd_kernel(
   coeff_bwd_body(cj, n_real, s, gbias, dpooled, partial, B, N, H, C, G, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// the backward in two parts (feta_coeff.h): the tanh pass over forward data, one (head, graph) block per workgroup ...
+__global__ __launch_bounds__(kCoeffThreads) void coeff_dsum_kernel(
+    const float* __restrict__ cj, const int32_t* __restrict__ n_real, const float* __restrict__ s,
+    const float* __restrict__ gbias, float* __restrict__ A, float* __restrict__ Bm, int B, int N, int C) {
+  coeff_dsum_body(cj, n_real, s, gbias, A, Bm, B, N, C, (int)blockIdx.x);
+}
+
+// ... and the part that depends on dpooled: (channel tile, block group)
+__global__ __launch_bounds__(kCoeffThreads) void coeff_bwd_saved_kernel(
+    const float* __restrict__ dpooled, const float* __restrict__ A, const float* __restrict__ Bm,
+    float* __restrict__ partial, int total, int C, int G) {
+  coeff_bwd_saved_body(dpooled, A, Bm, partial, total, C, G, (int)blockIdx.x, (int)blockIdx.y);
+}
+
 // out[c] = sum_r in[r][c]: 16 columns x 64 row slices per workgroup (64-byte row segments),
 // pairwise LDS tree over the slices; deterministic.
 constexpr int kCsCols = 16, kCsSlices = 64;
@@ -297,6 +311,40 @@ extern "C" int feta_coeff_bwd(const float* cj, const int32_t* n_real, const floa
   if (dbias == ds + C)  // contiguous outputs: one reduction launch for both
     return launch_colsum(partial, ds, G, 2 * C, (hipStream_t)stream);
   // separate outputs: reduce the two interleaved halves one after the other
+  rc = launch_colsum_strided(partial, ds, G, C, 2 * C, (hipStream_t)stream);
+  if (rc != FETA_OK) return rc;
+  return launch_colsum_strided(partial + C, dbias, G, C, 2 * C, (hipStream_t)stream);
+}
+
+extern "C" int feta_coeff_dsum(const float* cj, const int32_t* n_real, const float* s, const float* gcn_bias, float* A,
+                               float* Bm, int B, int N, int H, int C, feta_stream_t stream) {
+  FETA_REQUIRE(cj && n_real && s && gcn_bias && A && Bm, "coeff_dsum: null pointer");
+  FETA_REQUIRE(B > 0 && H > 0 && C > 0 && N > 0, "coeff_dsum: empty shape");
+  auto kern = coeff_dsum_kernel;
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(kCoeffThreads), N * sizeof(float), (hipStream_t)stream, cj, n_real, s,
+                     gcn_bias, A, Bm, B, N, C);
+  return check_launch("feta_coeff_dsum");
+}
+
+extern "C" int feta_coeff_bwd_saved_groups(int B, int H) { return (B < 1 || H < 1) ? 0 : coeff_bwd_saved_groups(B * H); }
+
+extern "C" int feta_coeff_bwd_saved(const float* dpooled, const float* A, const float* Bm, float* partial, float* ds,
+                                    float* dbias, float* dw_dense, int dw_rows, int B, int H, int C,
+                                    feta_stream_t stream) {
+  FETA_REQUIRE(dpooled && A && Bm && partial && (ds == nullptr || dbias != nullptr), "coeff_bwd_saved: null pointer");
+  FETA_REQUIRE(B > 0 && H > 0 && C > 0, "coeff_bwd_saved: empty shape");
+  const int G = coeff_bwd_saved_groups(B * H);
+  const dim3 grid((C + kCoeffThreads - 1) / kCoeffThreads, G), block(kCoeffThreads);
+  auto kern = coeff_bwd_saved_kernel;
+  hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, dpooled, A, Bm, partial, B * H, C, G);
+  int rc = check_launch("feta_coeff_bwd_saved");
+  if (rc != FETA_OK || ds == nullptr) return rc;   // ds == NULL: the caller reduces the [G, 2C] partials itself
+  if (dw_dense != nullptr) {
+    FETA_REQUIRE(dw_rows > 0, "coeff_bwd_saved: dw_dense needs dw_rows");
+    feta_colsum_seg segs[2] = {{partial, ds, G, C, 2 * C, dw_dense, dw_rows}, {partial + C, dbias, G, C, 2 * C, nullptr, 0}};
+    return launch_colsum_multi(segs, 2, (hipStream_t)stream);
+  }
+  if (dbias == ds + C) return launch_colsum(partial, ds, G, 2 * C, (hipStream_t)stream);
   rc = launch_colsum_strided(partial, ds, G, C, 2 * C, (hipStream_t)stream);
   if (rc != FETA_OK) return rc;
   return launch_colsum_strided(partial + C, dbias, G, C, 2 * C, (hipStream_t)stream);

@@ -329,6 +329,94 @@ __device__ __forceinline__ void coeff_bwd_body(
   }
 }
 
+// ---- the backward in two parts (saved form) --------------------------------------------------------------------------
+// Per channel the backward above is  ds[c] = sum_blk dpooled[blk,c] A[blk,c],  db[c] = sum_blk dpooled[blk,c] Bm[blk,c]  with
+//   A[blk,c] = (1/n_blk) sum_i (1 - z^2) c_i,   Bm[blk,c] = (1/n_blk) sum_i (1 - z^2),   z = tanh(c_i s[c] + gb[c]):
+// A and Bm hold every tanh and depend on forward data only, so they can be computed anywhere between the forward and the
+// backward (coeff_dsum_body: a role of the filter stage's forward launch, which leaves most of the chip empty), and what
+// stays behind the dX GEMM is a multiply-and-column-sum without a transcendental (coeff_bwd_saved_body).
+
+// body of one (head, graph) block `blk`: A[blk, :] and Bm[blk, :]; 256 threads, dynamic LDS N floats.  A workgroup that
+// walks several blocks calls it once per block (the leading barrier protects the c_j row of the block before).
+__device__ __forceinline__ void coeff_dsum_body(
+    const float* __restrict__ cj, const int32_t* __restrict__ n_real, const float* __restrict__ s,
+    const float* __restrict__ gbias, float* __restrict__ A, float* __restrict__ Bm, int B, int N, int C, int blk) {
+  float* cjs = feta_lds;   // [N]
+  const int n = min(n_real[blk % B], N);
+  __syncthreads();
+  for (int i = threadIdx.x; i < N; i += kCoeffThreads) cjs[i] = cj[(int64_t)blk * N + i];
+  __syncthreads();
+  const float inv_n = n > 0 ? 1.0f / (float)n : 0.0f;
+  // four channels of a thread advance together through the node loop (see coeff_fwd_body)
+  for (int c0 = threadIdx.x; c0 < C; c0 += 4 * kCoeffThreads) {
+    float sc[4], bc[4], as[4], ab[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = min(c0 + k * kCoeffThreads, C - 1);
+      sc[k] = s[c];
+      bc[k] = gbias[c];
+      as[k] = ab[k] = 0.0f;
+    }
+#pragma unroll 2
+    for (int i = 0; i < n; ++i) {
+      const float ci = cjs[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float z = fast_tanh(ci * sc[k] + bc[k]);
+        const float t = 1.0f - z * z;
+        as[k] += t * ci;
+        ab[k] += t;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = c0 + k * kCoeffThreads;
+      if (c < C) {
+        A[(int64_t)blk * C + c] = as[k] * inv_n;
+        Bm[(int64_t)blk * C + c] = ab[k] * inv_n;
+      }
+    }
+  }
+}
+
+// Groups of the saved-form backward: as a role it trails the 480 main workgroups of the last layer's ffn_bwd, which leave
+// 32 of the 512 resident slots free - 4 channel tiles (C = 1024) x 8 groups; beyond 512 blocks a group still walks at most 64.
+__host__ __device__ inline int coeff_bwd_saved_groups(int total) {
+  const int g = total / 64 > 8 ? total / 64 : 8;
+  return total < g ? total : g;
+}
+
+// body of one (channel tile `bx` of 256, block group `grp` of G): partial[grp][0][c] = sum_{blk in grp} dpooled A,
+// partial[grp][1][c] the same with Bm; blk = grp, grp + G, ... - the loads of kCoeffSavedPass blocks are requested before the
+// first add, and the adds run in block order (a function of the shapes alone).  No LDS.
+constexpr int kCoeffSavedPass = 8;
+__device__ __forceinline__ void coeff_bwd_saved_body(
+    const float* __restrict__ dpooled, const float* __restrict__ A, const float* __restrict__ Bm,
+    float* __restrict__ partial, int total, int C, int G, int bx, int grp) {
+  const int c = bx * kCoeffThreads + threadIdx.x;
+  const int cc = c < C ? c : C - 1;
+  float as = 0.0f, ab = 0.0f;
+  for (int blk0 = grp; blk0 < total; blk0 += G * kCoeffSavedPass) {
+    float dp[kCoeffSavedPass], av[kCoeffSavedPass], bv[kCoeffSavedPass];
+#pragma unroll
+    for (int u = 0; u < kCoeffSavedPass; ++u) {
+      const int blk = blk0 + u * G;
+      const int64_t o = (int64_t)(blk < total ? blk : total - 1) * C + cc;
+      dp[u] = blk < total ? dpooled[o] : 0.0f;   // (a block past the end adds exact zeros)
+      av[u] = blk < total ? A[o] : 0.0f;
+      bv[u] = blk < total ? Bm[o] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < kCoeffSavedPass; ++u) {
+      as += dp[u] * av[u];
+      ab += dp[u] * bv[u];
+    }
+  }
+  if (c < C) {
+    partial[(int64_t)grp * 2 * C + c] = as;      // [G][2][C], as coeff_bwd_body
+    partial[(int64_t)grp * 2 * C + C + c] = ab;
+  }
+}
 
 // staging mode of a block's attention rows as a ROLE (48 KB tile budget): 1 = N <= 64 (64 x 4 thread layout), 2 = larger
 // graphs (float4 column groups x row slices, pitch N rounded up to 4), 0 = not staged.  The stand-alone launch
@@ -350,6 +438,11 @@ struct CoeffFwdRole {
 struct CoeffBwdRole {
   const float* cj; const int32_t* n_real; const float* s; const float* gbias; const float* dpooled; float* partial;
   int B, N, H, C, G;
+  const float* A; const float* Bm;   // saved form (coeff_bwd_saved_body: cj, n_real, s, gbias unused, G its groups) or NULL
+};
+struct CoeffDsumRole {
+  const float* cj; const int32_t* n_real; const float* s; const float* gbias; float* A; float* Bm;
+  int B, N, H, C;
 };
 
 }  // namespace feta

@@ -93,8 +93,14 @@ __global__ __launch_bounds__(kRowThreads) void ffn_bwd_kernel(FfnGradArgs a, Ffn
   if (bid < ge.role_lead || bid >= ge.role_lead + ge.main_grid) {
     const int r = bid < ge.role_lead ? bid : bid - ge.main_grid;
     const int nbx = (cb.C + kCoeffThreads - 1) / kCoeffThreads;
-    if (r < ge.role)
-      coeff_bwd_body(cb.cj, cb.n_real, cb.s, cb.gbias, cb.dpooled, cb.partial, cb.B, cb.N, cb.H, cb.C, cb.G, r % nbx, r / nbx);
+    if (r < ge.role) {
+      // saved form (A / Bm from the filter stage's forward launch): a multiply-and-column-sum, 32 workgroups at the headline
+      // shape - they fit the slots the main grid leaves free and TRAIL it
+      if (cb.A != nullptr)
+        coeff_bwd_saved_body(cb.dpooled, cb.A, cb.Bm, cb.partial, cb.B * cb.H, cb.C, cb.G, r % nbx, r / nbx);
+      else
+        coeff_bwd_body(cb.cj, cb.n_real, cb.s, cb.gbias, cb.dpooled, cb.partial, cb.B, cb.N, cb.H, cb.C, cb.G, r % nbx, r / nbx);
+    }
     return;
   }
   bid -= ge.role_lead;
@@ -570,8 +576,9 @@ int launch_ffn_bwd(const FfnGradArgs& a, const CoeffBwdRole& cb, hipStream_t str
   ge.per = (nrb16 + ge.RC - 1) / ge.RC;
   ge.NS = FF / kFbSlice;
   size_t lds = ffn_bwd_lds_bytes<T>(FF, a.g_bn != nullptr);
-  const int role = cb.cj != nullptr ? ((cb.C + kCoeffThreads - 1) / kCoeffThreads) * cb.G : 0;
-  if (role > 0 && sizeof(float) * (size_t)(kCoeffPass * cb.N) > lds) lds = sizeof(float) * (size_t)(kCoeffPass * cb.N);
+  const bool saved = cb.A != nullptr;
+  const int role = (cb.cj != nullptr || saved) ? ((cb.C + kCoeffThreads - 1) / kCoeffThreads) * cb.G : 0;
+  if (role > 0 && !saved && sizeof(float) * (size_t)(kCoeffPass * cb.N) > lds) lds = sizeof(float) * (size_t)(kCoeffPass * cb.N);
   auto kern = ffn_bwd_kernel<T, FF>;
   static LdsSeen seen;
   allow_dynamic_lds(kern, lds, seen);
@@ -597,6 +604,10 @@ int launch_ffn_bwd(const FfnGradArgs& a, const CoeffBwdRole& cb, hipStream_t str
   ge.role = role;
   ge.role_lead = 8 * ((role + 7) / 8);
   if (const char* e = getenv("FETA_COEFF_ROLE_FIRST")) if (atoi(e) == 0) ge.role_lead = 0;
+  if (saved) {   // FETA_COEFF_SAVED_LEAD=1: in front, as the tanh form (A/B)
+    const char* e = getenv("FETA_COEFF_SAVED_LEAD");
+    if (e == nullptr || atoi(e) == 0) ge.role_lead = 0;
+  }
   hipLaunchKernelGGL(kern, dim3(grid + (ge.role_lead > 0 ? ge.role_lead : role)), dim3(kRowThreads), lds, stream, a, ge, cb);
   return check_launch("feta_ffn_bwd");
 }
@@ -610,6 +621,8 @@ extern "C" int feta_ffn_bwd_supported(int d_model, int ff) { return (d_model == 
 extern "C" int feta_ffn_bwd_blocks(int M) { return ffn_bwd_xblocks(M); }
 extern "C" int feta_ffn_bwd_chunks(int M, int ff) { return (M < 1 || !feta_ffn_bwd_supported(kFbD, ff)) ? 0 : ffn_bwd_chunks_for(M, ff); }
 
+static int ffn_bwd_checked(const feta_ffn_grad* d, const CoeffBwdRole& cb, feta_stream_t stream);
+
 extern "C" int feta_ffn_bwd(const feta_ffn_grad* d, feta_stream_t stream) { return feta_ffn_bwd_coeff(d, nullptr, stream); }
 
 extern "C" int feta_ffn_bwd_coeff(const feta_ffn_grad* d, const feta_coeff_bwd_role* c, feta_stream_t stream) {
@@ -619,8 +632,22 @@ extern "C" int feta_ffn_bwd_coeff(const feta_ffn_grad* d, const feta_coeff_bwd_r
     FETA_REQUIRE(c->cj && c->n_real && c->s && c->gcn_bias && c->dpooled && c->partial, "ffn_bwd_coeff: null pointer");
     FETA_REQUIRE(c->B > 0 && c->H > 0 && c->C > 0 && c->N > 0, "ffn_bwd_coeff: empty shape");
     cb = CoeffBwdRole{c->cj, c->n_real, c->s, c->gcn_bias, c->dpooled, c->partial, c->B, c->N, c->H, c->C,
-                      feta_coeff_bwd_groups(c->B, c->H)};
+                      feta_coeff_bwd_groups(c->B, c->H), nullptr, nullptr};
   }
+  return ffn_bwd_checked(d, cb, stream);
+}
+
+extern "C" int feta_ffn_bwd_coeff_saved(const feta_ffn_grad* d, const feta_coeff_bwd_saved_role* c, feta_stream_t stream) {
+  FETA_REQUIRE(d != nullptr && c != nullptr, "ffn_bwd_coeff_saved: null descriptor");
+  FETA_REQUIRE(c->dpooled && c->A && c->Bm && c->partial, "ffn_bwd_coeff_saved: null pointer");
+  FETA_REQUIRE(c->B > 0 && c->H > 0 && c->C > 0, "ffn_bwd_coeff_saved: empty shape");
+  CoeffBwdRole cb{};
+  cb.dpooled = c->dpooled; cb.partial = c->partial; cb.A = c->A; cb.Bm = c->Bm;
+  cb.B = c->B; cb.H = c->H; cb.C = c->C; cb.G = coeff_bwd_saved_groups(c->B * c->H);
+  return ffn_bwd_checked(d, cb, stream);
+}
+
+static int ffn_bwd_checked(const feta_ffn_grad* d, const CoeffBwdRole& cb, feta_stream_t stream) {
   const FfnGradArgs& a = *d;
   FETA_REQUIRE(a.dy && a.h && a.w2 && a.w1 && a.x && a.dx && a.partial && a.M > 0, "ffn_bwd: null pointer / empty");
   FETA_REQUIRE(feta_ffn_bwd_supported(kFbD, a.FF), "ffn_bwd: dim_feedforward %d not in {64,128}", a.FF);

@@ -12,7 +12,10 @@
 //
 // Tile conventions: feta_tiles.h.  "acc layout" of a [rows x cols] tile means register
 // r of lane (g, lq) holds element (row 4g + r, column lq).
+#include <cstdlib>
+
 #include "feta_abi_common.h"
+#include "feta_coeff.h"
 #include "feta_rowops.h"
 #include "feta_tiles.h"
 
@@ -1396,8 +1399,24 @@ __host__ __device__ inline int spec_cat_fwd_lds_floats(int pp) {
          reduce_scratch_floats(kCatD, 256);
 }
 
-template <int NT_MAX, int ET_MAX, int PP>
-__global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, CatArgs c) {
+// The launch can carry the tanh pass of the coefficient generator's BACKWARD (coeff_dsum_body, feta_coeff.h) in trailing
+// workgroups (ROLE = true: feta_spec_filter_cat_fwd_coeff): that pass needs forward data only, and this launch runs one
+// workgroup per graph - 128 at the headline batch, on 256 CUs that hold two of them each (~59 KB of LDS per workgroup).
+// cr.grid workgroups behind the a.B main ones walk the (head, graph) blocks r, r + cr.grid, ...; the main workgroups run the
+// same code with and without the role.
+template <bool ROLE> struct CoeffDsumHost {};
+template <> struct CoeffDsumHost<true> { CoeffDsumRole r; int grid; };
+
+template <int NT_MAX, int ET_MAX, int PP, bool ROLE = false>
+__global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, CatArgs c, CoeffDsumHost<ROLE> cr) {
+  if constexpr (ROLE) {
+    if ((int)blockIdx.x >= a.B) {
+      const int total = cr.r.B * cr.r.H;
+      for (int blk = (int)blockIdx.x - a.B; blk < total; blk += cr.grid)
+        coeff_dsum_body(cr.r.cj, cr.r.n_real, cr.r.s, cr.r.gbias, cr.r.A, cr.r.Bm, cr.r.B, cr.r.N, cr.r.C, blk);
+      return;
+    }
+  }
   constexpr int DH = 16, XP = kGraphXP, UP = 16 * ET_MAX + 4, WP = kGraphWP, NR = 16 * NT_MAX, D = kCatD, YP = D + 4;
   const int tid = threadIdx.x, lane = tid & 63, h = tid >> 6, lq = lane & 15, g = lane >> 4;
   const int b = blockIdx.x;
@@ -1597,13 +1616,61 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
   }
 }
 
+// Role workgroups of that launch.  One round of resident workgroups is (CUs) x (workgroups per CU), both asked of the runtime
+// for the instantiation and its dynamic LDS (MI355X: 256 CUs; two per CU for K <= 16, one for K <= 32, whose instantiations
+// compile to one wave per SIMD).  The role takes what the main grid leaves free of its last round, at most one workgroup per
+// block, and a role workgroup walks at most kCatRoleWalkMax blocks - the launch is on the forward's critical chain, and a
+// longer walk (a batch that nearly fills a round: B = 500 leaves 12 slots for 2000 blocks) would outlast the main
+// workgroups by far.  Where that does not fit the role is not taken (feta_spec_cat_fwd_coeff_fits: the caller keeps the
+// backward that recomputes the tanh).  FETA_COEFF_DSUM_WGS=n: n role workgroups whatever the walk (A/B timing, tests).
+constexpr int kCatRoleWalkMax = 2;
 template <int NT_MAX, int ET_MAX>
-int launch_spec_cat_fwd(const FilterArgs& a, const CatArgs& c, hipStream_t stream) {
-  const size_t lds = sizeof(float) * spec_cat_fwd_lds_floats<NT_MAX, ET_MAX>(4);
-  auto kern = spec_cat_fwd_graph_kernel<NT_MAX, ET_MAX, 4>;
+int spec_cat_fwd_slots() {
+  static int slots = 0;      // (per instantiation; the first call comes before any capture)
+  if (slots == 0) {
+    const size_t lds = sizeof(float) * spec_cat_fwd_lds_floats<NT_MAX, ET_MAX>(4);
+    auto kern = spec_cat_fwd_graph_kernel<NT_MAX, ET_MAX, 4, true>;
+    static LdsSeen lds_seen;
+    allow_dynamic_lds(kern, lds, lds_seen);
+    int dev = 0, cus = 0, per = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, 256, lds) != hipSuccess || cus < 1 || per < 1) {
+      (void)hipGetLastError();
+      return 0;      // unknown residency: no role
+    }
+    slots = cus * per;
+  }
+  return slots;
+}
+// -> role workgroups for `total` blocks beside B main workgroups, 0 if the role does not fit
+inline int spec_cat_fwd_role_grid(int slots, int B, int total) {
+  if (const char* e = getenv("FETA_COEFF_DSUM_WGS")) if (atoi(e) > 0) return atoi(e) < total ? atoi(e) : total;
+  if (slots < 1) return 0;
+  const int free_slots = slots - B % slots;
+  const int grid = total < free_slots ? total : free_slots;
+  return (total + grid - 1) / grid <= kCatRoleWalkMax ? grid : 0;
+}
+
+template <int NT_MAX, int ET_MAX>
+int launch_spec_cat_fwd(const FilterArgs& a, const CatArgs& c, const CoeffDsumRole* cr, hipStream_t stream) {
+  size_t lds = sizeof(float) * spec_cat_fwd_lds_floats<NT_MAX, ET_MAX>(4);
+  if constexpr (NT_MAX <= 4) {      // (the role takes graphs of up to 64 nodes)
+    if (cr != nullptr) {
+      if (sizeof(float) * (size_t)cr->N > lds) lds = sizeof(float) * (size_t)cr->N;
+      const int role = spec_cat_fwd_role_grid(spec_cat_fwd_slots<NT_MAX, ET_MAX>(), a.B, cr->B * cr->H);
+      FETA_REQUIRE(role > 0, "spec_filter_cat_fwd_coeff: %d blocks do not fit the slots %d graphs leave free (feta_spec_cat_fwd_coeff_fits)",
+                   cr->B * cr->H, a.B);
+      auto kern = spec_cat_fwd_graph_kernel<NT_MAX, ET_MAX, 4, true>;
+      static LdsSeen lds_seen;
+      allow_dynamic_lds(kern, lds, lds_seen);
+      hipLaunchKernelGGL(kern, dim3(a.B + role), dim3(256), lds, stream, a, c, CoeffDsumHost<true>{*cr, role});
+      return check_launch("feta_spec_filter_cat_fwd_coeff");
+    }
+  }
+  auto kern = spec_cat_fwd_graph_kernel<NT_MAX, ET_MAX, 4, false>;
   static LdsSeen lds_seen;
   allow_dynamic_lds(kern, lds, lds_seen);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds, stream, a, c);
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds, stream, a, c, CoeffDsumHost<false>{});
   return check_launch("feta_spec_filter_cat_fwd");
 }
 
@@ -2195,6 +2262,33 @@ extern "C" int feta_spec_filter_cat_fwd(const float* x, int64_t x_sb, int64_t x_
                                         const float* coeff, const float* bias, const int32_t* n_real, float* y,
                                         int64_t y_sb, int64_t y_sn, int B, int N, int H, int dh, int P, int K,
                                         int heads_share_graph, const feta_spec_cat* cat, feta_stream_t stream) {
+  return feta_spec_filter_cat_fwd_coeff(x, x_sb, x_sn, u, lam, coeff, bias, n_real, y, y_sb, y_sn, B, N, H, dh, P, K,
+                                        heads_share_graph, cat, nullptr, stream);
+}
+
+extern "C" int feta_spec_cat_fwd_coeff_fits(int B, int N, int K, int blocks) {
+  const int nt = (N + 15) / 16, et = (K + 15) / 16;
+  if (B < 1 || blocks < 1 || nt < 1 || nt > 4 || et < 1 || et > 2) return 0;
+  const int slots = nt <= 3 ? (et <= 1 ? spec_cat_fwd_slots<3, 1>() : spec_cat_fwd_slots<3, 2>())
+                            : (et <= 1 ? spec_cat_fwd_slots<4, 1>() : spec_cat_fwd_slots<4, 2>());
+  return spec_cat_fwd_role_grid(slots, B, blocks) > 0 ? 1 : 0;
+}
+
+extern "C" int feta_spec_filter_cat_fwd_coeff(const float* x, int64_t x_sb, int64_t x_sn, const float* u, const float* lam,
+                                              const float* coeff, const float* bias, const int32_t* n_real, float* y,
+                                              int64_t y_sb, int64_t y_sn, int B, int N, int H, int dh, int P, int K,
+                                              int heads_share_graph, const feta_spec_cat* cat,
+                                              const feta_coeff_dsum_role* role, feta_stream_t stream) {
+  CoeffDsumRole crv{};
+  const CoeffDsumRole* cr = nullptr;
+  if (role != nullptr) {
+    FETA_REQUIRE(role->cj && role->n_real && role->s && role->gcn_bias && role->A && role->Bm,
+                 "spec_filter_cat_fwd_coeff: null pointer");
+    FETA_REQUIRE(role->B > 0 && role->H > 0 && role->C > 0 && role->N > 0 && role->N <= 64,
+                 "spec_filter_cat_fwd_coeff: need 0 < N <= 64 (got %d)", role->N);
+    crv = CoeffDsumRole{role->cj, role->n_real, role->s, role->gcn_bias, role->A, role->Bm, role->B, role->N, role->H, role->C};
+    cr = &crv;
+  }
   FilterArgs a{};
   a.x = x; a.u = u; a.lam = lam; a.coeff = coeff; a.bias = bias; a.n_real = n_real; a.y = y;
   a.xsb = x_sb; a.xsn = x_sn; a.ysb = y_sb; a.ysn = y_sn;
@@ -2218,7 +2312,8 @@ extern "C" int feta_spec_filter_cat_fwd(const float* x, int64_t x_sb, int64_t x_
   c.w_cat = cat->w_cat; c.b_cat = cat->b_cat; c.out = cat->out;
   const int nt = (N + 15) / 16, et = (K + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
-  if (nt <= 3) return et <= 1 ? launch_spec_cat_fwd<3, 1>(a, c, st) : launch_spec_cat_fwd<3, 2>(a, c, st);
-  if (nt <= 4) return et <= 1 ? launch_spec_cat_fwd<4, 1>(a, c, st) : launch_spec_cat_fwd<4, 2>(a, c, st);
-  return et <= 1 ? launch_spec_cat_fwd<8, 1>(a, c, st) : launch_spec_cat_fwd<8, 2>(a, c, st);
+  if (nt <= 3) return et <= 1 ? launch_spec_cat_fwd<3, 1>(a, c, cr, st) : launch_spec_cat_fwd<3, 2>(a, c, cr, st);
+  if (nt <= 4) return et <= 1 ? launch_spec_cat_fwd<4, 1>(a, c, cr, st) : launch_spec_cat_fwd<4, 2>(a, c, cr, st);
+  FETA_REQUIRE(cr == nullptr, "spec_filter_cat_fwd_coeff: the role needs N <= 64 in the filter launch too");
+  return et <= 1 ? launch_spec_cat_fwd<8, 1>(a, c, nullptr, st) : launch_spec_cat_fwd<8, 2>(a, c, nullptr, st);
 }

@@ -7,6 +7,7 @@ produced in place: no transposes, no gathers, no scatter into zero-initialised b
 import torch
 
 from . import _lib
+from ._abi import CoeffSavedReq
 
 
 def _token_view(t, batch_first, heads):
@@ -126,6 +127,11 @@ class FilterCoefficientsFn(torch.autograd.Function):
             abi.coeff_fwd(attn, n_real, s, gb, cj, pooled, stream)
         if pending is not None:
             pending.coeff_fwd_req = None
+            pending.coeff_dsum_req = pending.coeff_dsum_out = None
+            if USE_COEFF_DSUM and pending.coeff_armed and n <= 64 and h * b <= COEFF_ROLE_MAX_BLOCKS:
+                # this node's backward will run: the filter stage's forward launch, which comes next and leaves most of the
+                # chip idle, may compute the tanh part of it (A, Bm: feta_coeff_dsum) - PendingSums.coeff_dsum_role
+                pending.coeff_dsum_req = (cj.detach(), n_real, s.detach(), gb.detach(), b, n, h)
         ctx.save_for_backward(cj, n_real, s, gb)
         ctx.dims = (b, n, h, gcn_weight.shape[0])
         return pooled
@@ -136,14 +142,41 @@ class FilterCoefficientsFn(torch.autograd.Function):
         b, n, h, rows = ctx.dims
         abi, stream = _lib.backend(cj)
         c = s.shape[0]
-        groups = abi.coeff_bwd_groups(b, h)
-        partial = torch.empty((groups, 2, c), dtype=torch.float32, device=cj.device)
         dsdb = torch.empty((2, c), dtype=torch.float32, device=cj.device)   # contiguous: one reduction
         ds, db = dsdb[0], dsdb[1]
         # s = 1^T W  =>  every row of dW equals ds: the reduction launch writes the dense rows itself (an
         # expanded view would be copied into a dense .grad by autograd: one more 4 MB kernel per step)
         dw = torch.empty((rows, c), dtype=torch.float32, device=cj.device)
         pend = ctx.pending
+        saved = None
+        if pend is not None:
+            saved, pend.coeff_dsum_out = pend.coeff_dsum_out, None
+            pend.coeff_dsum_req = None
+        if saved is not None and torch.is_grad_enabled():
+            saved = None        # a backward under grad mode (create_graph=True): the earlier form, as it stands
+        if saved is not None:
+            # A / Bm exist (the filter stage's forward launch carried the tanh pass): what is left is a multiply-and-column-
+            # sum - as trailing workgroups of the stack's first backward launch, or on its own
+            A, Bm = saved
+            sg = abi.coeff_bwd_saved_groups(b, h)
+            partial = torch.empty((sg, 2, c), dtype=torch.float32, device=cj.device)
+            dpc = dpooled.contiguous()
+            if (pend.stack_armed and not pend.stack_done and PendingSums.untouched(*ctx.params)):
+                pend.coeff_bwd_req = CoeffSavedReq(dpc, A, Bm, partial, b, h)
+                p2 = partial.view(sg, 2 * c)
+                pend.add(p2[:, :c], ds, dw, owners=[(ctx.params[0], dw)])
+                pend.add(p2[:, c:], db, owners=[(ctx.params[1], db)])
+                return None, None, dw, db, None
+            waiting = pend.take()
+            if waiting:
+                abi.coeff_bwd_saved(dpc, A, Bm, partial, None, None, b, h, stream)
+                p2 = partial.view(sg, 2 * c)
+                abi.colsum_multi([(p2[:, :c], ds, dw), (p2[:, c:], db)] + waiting, stream)
+            else:
+                abi.coeff_bwd_saved(dpc, A, Bm, partial, ds, db, b, h, stream, dw_dense=dw)
+            return None, None, dw, db, None
+        groups = abi.coeff_bwd_groups(b, h)
+        partial = torch.empty((groups, 2, c), dtype=torch.float32, device=cj.device)
         if (pend is not None and pend.stack_armed and not pend.stack_done and PendingSums.untouched(*ctx.params)):
             # the layer stack's backward comes after this node: its first launch carries this node's kernel in trailing
             # workgroups (feta_ffn_bwd_coeff), its reduction launch the sums
@@ -251,6 +284,11 @@ LIN_LIB_BF16_MIN_ROWS = int(_os.environ.get('FETA_LIN_LIB_BF16_MIN_ROWS', '2048'
 # launches (eight waves per SIMD) are the faster form even with their launch cost: config 5 (4096 blocks) 1.040 -> 1.022 ms
 # per step, the BASELINE batch (512 blocks) and config 4 (256 blocks of 128 nodes) the other way round.
 COEFF_ROLE_MAX_BLOCKS = int(_os.environ.get('FETA_COEFF_ROLE_MAX', 2048))
+# The tanh pass of the coefficient generator's backward (A, Bm: feta_coeff_dsum) rides in the filter stage's forward launch,
+# and what stays in the stack's first backward launch is a multiply-and-column-sum (csrc/feta_coeff.h).  FETA_COEFF_DSUM=0:
+# off - the backward recomputes the tanh in that launch, as before (A/B timing; EXPERIMENTS.md: 0.2579 -> 0.2535 ms at the
+# headline, the last layer's ffn_bwd 19.6 -> 13.4 us, the filter launch 9.9 -> 11.0 us).
+USE_COEFF_DSUM = _os.environ.get('FETA_COEFF_DSUM', '1') != '0'
 
 
 class PendingSums:
@@ -280,6 +318,26 @@ class PendingSums:
         self.coeff_fwd_req = None
         self.coeff_fwd_out = None
         self.coeff_bwd_req = None
+        # ... and the tanh pass of that backward: coeff_dsum_req = (cj, n_real, s, gcn_bias, b, n, h), left by
+        # FilterCoefficientsFn.forward when its backward will run; coeff_dsum_out = (A, Bm) once the filter stage's forward
+        # launch has taken it (detached tensors only: this object is reachable from the autograd nodes of the stage)
+        self.coeff_dsum_req = None
+        self.coeff_dsum_out = None
+
+    def coeff_dsum_role(self, abi, graphs, k_eig):
+        """Called by the forward that launches feta_spec_filter_cat_fwd for `graphs` graphs on k_eig eigenvectors: -> the
+        argument tuple of abi.coeff_dsum (A and Bm allocated here), or None if nobody asked or the blocks do not fit the
+        slots that launch leaves free (a role workgroup walks at most two blocks: the launch is on the forward's chain)."""
+        req, self.coeff_dsum_req = self.coeff_dsum_req, None
+        if req is None:
+            return None
+        cj, n_real, s, gb, b, n, h = req
+        if not abi.spec_cat_fwd_coeff_fits(graphs, n, k_eig, h * b):
+            return None
+        A = torch.empty((h * b, s.shape[0]), dtype=torch.float32, device=cj.device)
+        Bm = torch.empty_like(A)
+        self.coeff_dsum_out = (A, Bm)
+        return (cj, n_real, s, gb, A, Bm, b, n, h)
 
     @staticmethod
     def untouched(*params):
@@ -347,7 +405,9 @@ class PendingSums:
         items = self.take()
         if items:
             abi, stream = _lib.backend(items[0][0])
-            if req is not None:
+            if isinstance(req, CoeffSavedReq):
+                req.run(abi, stream)
+            elif req is not None:
                 cj, n_real, s, gb, dpooled, partial, b, n, h = req
                 abi.coeff_bwd(cj, n_real, s, gb, dpooled, partial, None, None, b, n, h, stream)
             abi.colsum_multi(items, stream)
@@ -459,8 +519,12 @@ class FilterFromPooledFn(torch.autograd.Function):
                 t, nm = cat.tail, cat.tail.norm
                 kw = dict(y2_stats=t.st2, Gx=t.G2, gamma=t.gamma, beta=t.beta, bn_out=t.prm2, rmean=nm.running_mean,
                           rvar=nm.running_var, nbt=nm.num_batches_tracked, momentum=float(nm.momentum), eps=float(nm.eps))
+            # (the coefficient generator's node ran just before this one: if its backward will run and this node's will
+            # too - pooled's gradient comes from here -, the tanh pass of that backward rides in this launch)
+            dsum = (pending.coeff_dsum_role(abi, b, g0.shape[2]) if (pending is not None and ctx.needs_input_grad[1])
+                    else None)
             abi.spec_filter_cat_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream, y2=y2v, w_cat=cat.w.detach().contiguous(),
-                                    b_cat=None if cat.bias is None else cat.bias.detach(), out=out, **kw)
+                                    b_cat=None if cat.bias is None else cat.bias.detach(), out=out, dsum=dsum, **kw)
             cat.out = out.permute(1, 0, 2, 3).reshape(n * b, h * dh)      # (a view: [N, B, d] rows)
             cat.y = y.detach()      # (another tensor object: the returned y gets this node as grad_fn - kept in ctx.cat it would be a cycle)
             cat.bwd_ok = bool(abi.spec_cat_bwd_supported(n, h, dh, order, g0.shape[2], share))
@@ -468,6 +532,8 @@ class FilterFromPooledFn(torch.autograd.Function):
             abi.cheb_filter_fwd(xs, g0, cw, bias, n_real, y, order, share, stream)
         else:
             abi.spec_filter_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream)
+        if pending is not None:
+            pending.coeff_dsum_req = None     # (not taken: the backward recomputes the tanh, as before)
         ctx.save_for_backward(xs, cw, pooled, lin_w, n_real, g0, g1)
         ctx.cfg = (mode, order, share, batch_first, bias is not None)
         ctx.cat = cat if fold else None

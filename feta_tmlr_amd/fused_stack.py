@@ -1065,8 +1065,15 @@ def _coeff_bwd_request(ctx, abi, stream, d, ff_last):
     (the last layer's fused FFN backward); run here on its own when that launch is not the fused kernel."""
     from . import functional as F
     req = ctx.pending.take_coeff_bwd() if ctx.pending is not None else None
-    if req is not None and (not (USE_FFN_BWD and abi.ffn_bwd_supported(d, ff_last))
-                            or req[6] * req[8] > F.COEFF_ROLE_MAX_BLOCKS):
+    if req is None:
+        return None
+    hosted = USE_FFN_BWD and abi.ffn_bwd_supported(d, ff_last)
+    if isinstance(req, F.CoeffSavedReq):     # the saved form (A / Bm from the filter stage's forward launch)
+        if not hosted:
+            req.run(abi, stream)
+            req = None
+        return req
+    if not hosted or req[6] * req[8] > F.COEFF_ROLE_MAX_BLOCKS:
         cj, n_real, s, gb, dpooled, partial, b, n, h = req
         abi.coeff_bwd(cj, n_real, s, gb, dpooled, partial, None, None, b, n, h, stream)
         req = None

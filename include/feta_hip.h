@@ -117,6 +117,19 @@ int feta_coeff_bwd(const float* cj, const int32_t* n_real,
                    float* partial, float* ds, float* dbias, float* dw_dense, int dw_rows,
                    int B, int N, int H, int C, feta_stream_t stream);
 
+/* The same backward in two parts (ABI 13, additive).  Per channel ds[c] = sum_blk dpooled[blk,c] A[blk,c] and
+ * dbias[c] = sum_blk dpooled[blk,c] Bm[blk,c] with
+ *   A[blk,c] = (1/n_blk) sum_i (1 - z^2) c_i,  Bm[blk,c] = (1/n_blk) sum_i (1 - z^2),  z = tanh(c_i s[c] + gcn_bias[c]):
+ * feta_coeff_dsum computes A and Bm ([H*B, C] each; zeros for a block with n_real = 0) from forward data alone - every tanh
+ * of the backward -, feta_coeff_bwd_saved the part that depends on dpooled.  partial [G, 2, C] with
+ * G = feta_coeff_bwd_saved_groups(B, H); ds / dbias / dw_dense as feta_coeff_bwd. */
+int feta_coeff_dsum(const float* cj, const int32_t* n_real, const float* s, const float* gcn_bias,
+                    float* A, float* Bm, int B, int N, int H, int C, feta_stream_t stream);
+int feta_coeff_bwd_saved_groups(int B, int H);
+int feta_coeff_bwd_saved(const float* dpooled, const float* A, const float* Bm,
+                         float* partial, float* ds, float* dbias, float* dw_dense, int dw_rows,
+                         int B, int H, int C, feta_stream_t stream);
+
 /* out[c] = sum_r in[r, c]  (s = colsum(gcn.weight); also reduces per-block partials) */
 int feta_colsum(const float* in, float* out, int R, int C, feta_stream_t stream);
 
@@ -235,6 +248,23 @@ int feta_spec_filter_cat_fwd(const float* x, int64_t x_sb, int64_t x_sn, const f
                              const float* coeff, const float* bias, const int32_t* n_real, float* y,
                              int64_t y_sb, int64_t y_sn, int B, int N, int H, int dh, int P, int K,
                              int heads_share_graph, const feta_spec_cat* cat, feta_stream_t stream);
+
+/* The same launch with feta_coeff_dsum (its arguments; N <= 64) in trailing workgroups: the launch runs one workgroup per
+ * graph and leaves most of the chip idle at small batches, and the tanh pass of the coefficient generator's backward needs
+ * forward data only.  role == NULL: feta_spec_filter_cat_fwd.  y, out and bn_out do not depend on the role.
+ * feta_spec_cat_fwd_coeff_fits(B, N, K, blocks): 1 if `blocks` role blocks fit beside the B main workgroups - the role takes
+ * the resident slots the main grid leaves free of its last round and a role workgroup walks at most two blocks; the launch
+ * with a role that does not fit is FETA_E_ARG (the caller then keeps feta_coeff_bwd). */
+int feta_spec_cat_fwd_coeff_fits(int B, int N, int K, int blocks);
+typedef struct feta_coeff_dsum_role {
+  const float* cj; const int32_t* n_real; const float* s; const float* gcn_bias; float* A; float* Bm;
+  int B, N, H, C;
+} feta_coeff_dsum_role;
+int feta_spec_filter_cat_fwd_coeff(const float* x, int64_t x_sb, int64_t x_sn, const float* u, const float* lam,
+                                   const float* coeff, const float* bias, const int32_t* n_real, float* y,
+                                   int64_t y_sb, int64_t y_sn, int B, int N, int H, int dh, int P, int K,
+                                   int heads_share_graph, const feta_spec_cat* cat, const feta_coeff_dsum_role* role,
+                                   feta_stream_t stream);
 
 /* Backward of the same fold (ABI 11): feta_spec_filter_bwd with the backward of linear_cat inside - replaces
  * feta_rowlin_bwd_ex over [x_n | filt] (functional.RowLinearCat[BN]Fn.backward, transformer/models.py:223-224 under
@@ -729,6 +759,13 @@ typedef struct feta_coeff_bwd_role {
   int B, N, H, C;
 } feta_coeff_bwd_role;
 int feta_ffn_bwd_coeff(const feta_ffn_grad* d, const feta_coeff_bwd_role* c, feta_stream_t stream);
+/* ... or its saved form (feta_coeff_bwd_saved with ds = NULL: A / Bm from feta_coeff_dsum, partial
+ * [feta_coeff_bwd_saved_groups(B, H), 2, C]); these workgroups trail the main ones. */
+typedef struct feta_coeff_bwd_saved_role {
+  const float* dpooled; const float* A; const float* Bm; float* partial;
+  int B, H, C;
+} feta_coeff_bwd_saved_role;
+int feta_ffn_bwd_coeff_saved(const feta_ffn_grad* d, const feta_coeff_bwd_saved_role* c, feta_stream_t stream);
 
 /* ---- the whole encoder stack for inference in ONE launch (ABI 12) ------------------------------------------
  * Forward of L DiffTransformerEncoderLayers (contract transformer/models.py:166-167,179,244; body per upstream GraphiT,
