@@ -595,6 +595,8 @@ class Abi:
                        b, n, h, dh, order, k, int(share), stream), nm)
 
     def spec_cat_supported(self, n, h, dh, order, k, share):
+        """feta_spec_cat_supported: 4 heads x 16 (n <= 128) or 8 heads x 8 (n <= 64), order 4, k <= 32 (a multiple of 4),
+        every head on the graph"""
         return bool(self.lib.feta_spec_cat_supported(n, h, dh, order, k, int(share)))
 
     def spec_cat_fwd_coeff_fits(self, b, n, k, blocks):
@@ -604,9 +606,10 @@ class Abi:
     def spec_filter_cat_fwd(self, x, u, lam, coeff, bias, n_real, y, order, share, stream, y2, w_cat, b_cat, out,
                             y2_bn=None, y2_stats=None, Gx=0, gamma=None, beta=None, bn_out=None, rmean=None, rvar=None,
                             nbt=None, momentum=0.1, eps=1e-5, dsum=None):
-        """feta_spec_filter_cat_fwd: the eigenbasis filter with linear_cat folded in.  y2 [N, B, 64] (or [B, N, 64]
-        batch-first like x) = the stack output, out like y.  dsum (optional): (cj, n_real, s, gcn_bias, A, Bm, b, n, h),
-        the arguments of coeff_dsum - it rides in trailing workgroups (feta_spec_filter_cat_fwd_coeff)."""
+        """feta_spec_filter_cat_fwd: the eigenbasis filter with linear_cat folded in, for x [B, N, 4, 16] or [B, N, 8, 8]
+        (spec_cat_supported).  y2 [N, B, 64] (or [B, N, 64] batch-first like x) = the stack output, out like y.  dsum
+        (optional, 4 heads only): (cj, n_real, s, gcn_bias, A, Bm, b, n, h), the arguments of coeff_dsum - it rides in
+        trailing workgroups (feta_spec_filter_cat_fwd_coeff)."""
         b, n, h, dh = x.shape
         k = u.shape[2]
         xsb, xsn = tok_strides(x)
@@ -634,6 +637,7 @@ class Abi:
                     'feta_spec_filter_cat_fwd')
 
     def spec_cat_bwd_supported(self, n, h, dh, order, k, share):
+        """feta_spec_cat_bwd_supported: the shapes of spec_cat_supported up to n = 64 (4 heads x 16 or 8 heads x 8)"""
         return bool(self.lib.feta_spec_cat_bwd_supported(n, h, dh, order, k, int(share)))
 
     def spec_cat_bwd_rows(self, b):
@@ -642,8 +646,9 @@ class Abi:
     def spec_filter_cat_bwd(self, x, u, lam, coeff, n_real, filt, dx, dcoeff, dbias_part, order, share, stream, dout, y2,
                             w_cat, dxn, partial, y2_bn=None, gs=None):
         """feta_spec_filter_cat_bwd: the eigenbasis filter's backward with the backward of linear_cat folded in.
-        x / filt / dx: [B, N, H, dh] token views; dout / y2 / dxn: [B, N, H, dh] views of [N, B, 64] row tensors (same
-        strides); partial [B, >= 64 * 128 + 64]; gs [B, 2, 64] with y2_bn."""
+        x / filt / dx: [B, N, H, dh] token views, (H, dh) = (4, 16) or (8, 8); dout / y2 / dxn: [B, N, H, dh] views of
+        [N, B, 64] row tensors (same strides); dcoeff [H*B, 4*dh*dh]; dbias_part [B*H, dh]; partial [rows, >= 64 * 128 + 64]
+        and gs [rows, 2, 64] (with y2_bn), rows = spec_cat_bwd_rows(B)."""
         b, n, h, dh = x.shape
         k = u.shape[2]
         xsb, xsn = tok_strides(x)

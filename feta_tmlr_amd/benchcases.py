@@ -120,9 +120,10 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
         brole = (rnd(heads * b, n), n_real, rnd(cgen), rnd(cgen), rnd(heads * b, cgen), new(cgrp, 2, cgen), b, n, heads)
         cbytes = b * (heads * cgen + heads * n) + cgrp * 2 * cgen
         from . import functional as _F
-        if _F.USE_COEFF_DSUM and n <= 64 and heads * b <= _F.COEFF_ROLE_MAX_BLOCKS:
+        if _F.USE_COEFF_DSUM and n <= 64 and heads == 4 and heads * b <= _F.COEFF_ROLE_MAX_BLOCKS:
             # ... in its saved form where the step takes it (the tanh pass rode in the filter stage's forward launch:
-            # feta_ffn_bwd_coeff_saved - a multiply-and-column-sum in trailing workgroups); the case keeps its name
+            # feta_ffn_bwd_coeff_saved - a multiply-and-column-sum in trailing workgroups; 4 heads only, as
+            # functional.FilterCoefficientsFn asks for it); the case keeps its name
             cgrp = abi.coeff_bwd_saved_groups(b, heads)
             brole = _F.CoeffSavedReq(rnd(heads * b, cgen), rnd(heads * b, cgen), rnd(heads * b, cgen), new(cgrp, 2, cgen),
                                      b, heads)

@@ -1407,7 +1407,11 @@ __host__ __device__ inline int spec_cat_fwd_lds_floats(int pp) {
 template <bool ROLE> struct CoeffDsumHost {};
 template <> struct CoeffDsumHost<true> { CoeffDsumRole r; int grid; };
 
-template <int NT_MAX, int ET_MAX, int PP, bool ROLE = false>
+// TWO: 8 heads of 8 (the idea of the attention-block kernels, csrc/block.hip): wave t's 16-column tile holds heads 2t and
+// 2t + 1.  Everything 64 wide is head-agnostic; what depends on d_h is the W_k tile of step (2) - block-diagonal, the two
+// 8 x 8 blocks of the wave's heads on the diagonal and staged zeros beside them, the same [P * 16][WP] footprint and the
+// same MFMA chain - and the filter's bias, one [8] vector for every head (column lq takes bias[lq & 7]).
+template <int NT_MAX, int ET_MAX, int PP, bool ROLE = false, bool TWO = false>
 __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, CatArgs c, CoeffDsumHost<ROLE> cr) {
   if constexpr (ROLE) {
     if ((int)blockIdx.x >= a.B) {
@@ -1431,7 +1435,8 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
   float* xss = YT + 16 * ET_MAX * YP;     // [2][64] scale | shift of the BatchNorm in front
   float* scr = xss + 2 * D;               // finalize scratch
   const float* U = a.u + (int64_t)b * a.N * a.K;
-  const float* w = a.coeff + ((int64_t)h * a.B + b) * PP * DH * DH;
+  // (TWO: head 2h's [P][8][8] block; head 2h + 1's is a.B blocks further on)
+  const float* w = TWO ? a.coeff + ((int64_t)2 * h * a.B + b) * PP * 64 : a.coeff + ((int64_t)h * a.B + b) * PP * DH * DH;
 
   // ---- requests: everything this workgroup reads, before the first value is consumed ---------------------------------
   PartialBatchT<32> pb;
@@ -1452,7 +1457,28 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
     const float4 v = *reinterpret_cast<const float4*>(U + (int64_t)min(node, nm1) * a.K + min(e, a.K - 4));
     uv[i] = keep4(node < n && e < a.K, v);
   }
-  {
+  if constexpr (TWO) {
+    // a head's block is PP * 16 float4, (k, c) = idx >> 1 and c' = 4 (idx & 1): head 2h + i goes to rows 16 k + 8 i + c,
+    // columns 8 i + c', and the other head's columns of those rows are zero
+    constexpr int WI = (PP * 16 + 63) / 64;
+    float4 wv[2][WI];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < WI; ++j)
+        wv[i][j] = reinterpret_cast<const float4*>(w + (int64_t)i * a.B * PP * 64)[min(lane + 64 * j, PP * 16 - 1)];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < WI; ++j) {
+        const int idx = lane + 64 * j;
+        if (idx < PP * 16) {
+          float* row = Ws + ((idx >> 4) * 16 + 8 * i + ((idx >> 1) & 7)) * WP + 4 * (idx & 1);
+          *reinterpret_cast<float4*>(row + 8 * i) = wv[i][j];
+          *reinterpret_cast<float4*>(row + 8 * (1 - i)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+      }
+  } else {
     float4 wv[PP];
 #pragma unroll
     for (int i = 0; i < PP; ++i) wv[i] = reinterpret_cast<const float4*>(w)[lane + 64 * i];
@@ -1468,9 +1494,9 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
   load_row<D>(wbf, c.w_cat + (int64_t)(DH * h + lq) * 2 * D + D, g);
   const float bcat = c.b_cat != nullptr ? c.b_cat[DH * h + lq] : 0.0f;
   const float lv = a.lam[(int64_t)b * a.K + min(tid, a.K - 1)];
-  const float bv = (a.bias != nullptr) ? a.bias[lq] : 0.0f;
+  const float bv = (a.bias != nullptr) ? a.bias[TWO ? lq & 7 : lq] : 0.0f;
   float4 bs4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (a.bias != nullptr) bs4 = *reinterpret_cast<const float4*>(a.bias + 4 * g);
+  if (a.bias != nullptr) bs4 = *reinterpret_cast<const float4*>(a.bias + 4 * (TWO ? g & 1 : g));
   float xg = 1.0f, xb = 0.0f, xk = 0.0f;
   if (c.y2_stats != nullptr && tid < D) {
     xg = c.gamma[tid];
@@ -1561,7 +1587,7 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
     load_row<D>(yf, YT + (16 * et + lq) * YP, g);
     ytp[et] = dot_rows<D>(yf, wbf, zero4());
   }
-  // (bias Wb^T)[o]: the filter's bias is one [16] vector for every head; this lane holds Wb[o][16 j + 4 g + s]
+  // (bias Wb^T)[o]: the filter's bias is one [d_h] vector for every head; this lane holds Wb[o][16 j + 4 g + s]
   float cbo = 0.0f;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -1654,7 +1680,14 @@ inline int spec_cat_fwd_role_grid(int slots, int B, int total) {
 template <int NT_MAX, int ET_MAX>
 int launch_spec_cat_fwd(const FilterArgs& a, const CatArgs& c, const CoeffDsumRole* cr, hipStream_t stream) {
   size_t lds = sizeof(float) * spec_cat_fwd_lds_floats<NT_MAX, ET_MAX>(4);
-  if constexpr (NT_MAX <= 4) {      // (the role takes graphs of up to 64 nodes)
+  if constexpr (NT_MAX <= 4) {      // (8 heads of 8 and the role take graphs of up to 64 nodes)
+    if (a.H == 8) {                 // no role at 8 heads: feta_spec_filter_cat_fwd_coeff refuses it
+      auto kern = spec_cat_fwd_graph_kernel<NT_MAX, ET_MAX, 4, false, true>;
+      static LdsSeen lds_seen;
+      allow_dynamic_lds(kern, lds, lds_seen);
+      hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds, stream, a, c, CoeffDsumHost<false>{});
+      return check_launch("feta_spec_filter_cat_fwd");
+    }
     if (cr != nullptr) {
       if (sizeof(float) * (size_t)cr->N > lds) lds = sizeof(float) * (size_t)cr->N;
       const int role = spec_cat_fwd_role_grid(spec_cat_fwd_slots<NT_MAX, ET_MAX>(), a.B, cr->B * cr->H);
@@ -1705,7 +1738,10 @@ __host__ __device__ inline int spec_cat_bwd_lds_floats() {
   return 2 * NR * kGraphXP + NR * UP + 16 * ET_MAX + 16 * ET_MAX * (kCatD + 4) + 2 * kCatD;
 }
 
-template <int NT_MAX, int ET_MAX, int PP>
+// TWO: 8 heads of 8, wave t's tile = heads 2t and 2t + 1 (see spec_cat_fwd_graph_kernel).  The W_k^T operand of step (3) is
+// the block-diagonal tile (selected in registers: no cross-head terms), dW_k of step (2) is the same 16 x 16 product whose
+// two diagonal 8 x 8 blocks go to dcoeff of their own heads, and dbias_part keeps the [item][d_h] contract.
+template <int NT_MAX, int ET_MAX, int PP, bool TWO = false>
 __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, CatGradArgs c) {
   constexpr int DH = 16, XP = kGraphXP, UP = 16 * ET_MAX + 4, NR = 16 * NT_MAX, D = kCatD, DP = D + 4;
   const int h = threadIdx.x >> 6, lane0 = threadIdx.x & 63;
@@ -1754,9 +1790,11 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
   const int item = b * a.H + h;
   const int n = a.n_real[b], nm1 = max(n - 1, 0);
   const float* U = a.u + (int64_t)b * a.N * a.K;
-  const int64_t blk = (int64_t)h * a.B + b;
-  const float* w = a.coeff + blk * PP * DH * DH;
-  float* dw = a.dcoeff + blk * PP * DH * DH;
+  // (TWO: the block of head 2h + (lq >> 3), the head of this lane's column: both the row of W_k it reads as an operand
+  // and the column of dW_k it holds belong to it)
+  const int64_t blk = TWO ? (int64_t)(2 * h + (lq >> 3)) * a.B + b : (int64_t)h * a.B + b;
+  const float* w = a.coeff + blk * PP * (TWO ? 64 : DH * DH);
+  float* dw = a.dcoeff + blk * PP * (TWO ? 64 : DH * DH);
   const int64_t rb = (int64_t)b * c.y2sb;
 
   // ---- requests ------------------------------------------------------------------------------------------------------
@@ -1779,7 +1817,13 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
   }
   float4 wr[PP];  // W_k[c = lq][c' = 4g .. 4g+3]
 #pragma unroll
-  for (int k = 0; k < PP; ++k) wr[k] = *reinterpret_cast<const float4*>(w + (k * DH + lq) * DH + 4 * g);
+  for (int k = 0; k < PP; ++k) {
+    if constexpr (TWO) {    // zero off the diagonal blocks: c' = 4g .. 4g + 3 is of head (g >> 1), c = lq of head (lq >> 3)
+      wr[k] = keep4((g >> 1) == (lq >> 3), *reinterpret_cast<const float4*>(w + (k * 8 + (lq & 7)) * 8 + 4 * (g & 1)));
+    } else {
+      wr[k] = *reinterpret_cast<const float4*>(w + (k * DH + lq) * DH + 4 * g);
+    }
+  }
   const float lv = a.lam[(int64_t)b * a.K + min(tid, a.K - 1)];
   // this lane's column of the stack-output and filter-output rows node = 16 nt + 4 g + r (k-slot g of step (nt, r))
   float xn[NT_MAX][4], fl[NT_MAX][4], xh[NT_MAX][4];
@@ -1880,7 +1924,8 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
     }
     dbs += shfl_xor(dbs, 16);
     dbs += shfl_xor(dbs, 32);
-    if (g == 0) a.dbias_part[(int64_t)item * DH + lq] = dbs;
+    // (TWO: item (b, head 2h + (lq >> 3)), column lq & 7 of its [8] row - the same address, b * 64 + col)
+    if (g == 0) a.dbias_part[TWO ? (int64_t)b * D + col : (int64_t)item * DH + lq] = dbs;
   }
 
   // ---- (2) dW_k[c][c'] = sum_e t_k(lam_e) Xtil[e][c] dYtil[e][c'] --------------------------------
@@ -1901,7 +1946,13 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
 #pragma unroll
   for (int k = 0; k < PP; ++k)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dw[(k * DH + 4 * g + r) * DH + lq] = dwa[k][r];
+    for (int r = 0; r < 4; ++r) {
+      if constexpr (TWO) {  // rows c = 4g + r of head (g >> 1), this lane's column of head (lq >> 3): the diagonal blocks only
+        if ((g >> 1) == (lq >> 3)) dw[(k * 8 + ((4 * g + r) & 7)) * 8 + (lq & 7)] = dwa[k][r];
+      } else {
+        dw[(k * DH + 4 * g + r) * DH + lq] = dwa[k][r];
+      }
+    }
 
   // ---- (3) dXtil[e][c] = sum_k t_k(lam_e) sum_c' dYtil[e][c'] W_k[c][c'] -------------------------
   f32x4 dxt[ET_MAX];
@@ -2018,6 +2069,13 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
 template <int NT_MAX, int ET_MAX>
 int launch_spec_cat_bwd(const FilterArgs& a, const CatGradArgs& c, hipStream_t stream) {
   const size_t lds = sizeof(float) * spec_cat_bwd_lds_floats<NT_MAX, ET_MAX>();
+  if (a.H == 8) {
+    auto kern = spec_cat_bwd_graph_kernel<NT_MAX, ET_MAX, 4, true>;
+    static LdsSeen lds_seen;
+    allow_dynamic_lds(kern, lds, lds_seen);
+    hipLaunchKernelGGL(kern, dim3(spec_cat_bwd_rows(a.B)), dim3(256), lds, stream, a, c);
+    return check_launch("feta_spec_filter_cat_bwd");
+  }
   auto kern = spec_cat_bwd_graph_kernel<NT_MAX, ET_MAX, 4>;
   static LdsSeen lds_seen;
   allow_dynamic_lds(kern, lds, lds_seen);
@@ -2219,12 +2277,14 @@ extern "C" int feta_spec_filter_bwd(const float* x, int64_t x_sb, int64_t x_sn, 
 
 extern "C" int feta_spec_cat_supported(int N, int H, int dh, int P, int K, int heads_share_graph) {
   const int nt = (N + 15) / 16, et = (K + 15) / 16;
-  return (heads_share_graph && H == 4 && dh == 16 && P == 4 && nt >= 1 && nt <= 8 && et <= 2 && (K & 3) == 0 && K >= 4) ? 1 : 0;
+  const bool heads = (H == 4 && dh == 16 && nt <= 8) || (H == 8 && dh == 8 && nt <= 4);   // 8 heads: where their stacks are fused
+  return (heads_share_graph && heads && P == 4 && nt >= 1 && et <= 2 && (K & 3) == 0 && K >= 4) ? 1 : 0;
 }
 
 extern "C" int feta_spec_cat_bwd_supported(int N, int H, int dh, int P, int K, int heads_share_graph) {
   const int nt = (N + 15) / 16, et = (K + 15) / 16;
-  return (heads_share_graph && H == 4 && dh == 16 && P == 4 && nt >= 1 && nt <= 4 && et <= 2 && (K & 3) == 0 && K >= 4) ? 1 : 0;
+  const bool heads = (H == 4 && dh == 16) || (H == 8 && dh == 8);
+  return (heads_share_graph && heads && P == 4 && nt >= 1 && nt <= 4 && et <= 2 && (K & 3) == 0 && K >= 4) ? 1 : 0;
 }
 
 extern "C" int feta_spec_cat_bwd_rows(int B) { return B < 1 ? 0 : spec_cat_bwd_rows(B); }
@@ -2239,7 +2299,7 @@ extern "C" int feta_spec_filter_cat_bwd(const float* x, int64_t x_sb, int64_t x_
   a.B = B; a.N = N; a.H = H; a.P = P; a.K = K; a.share = heads_share_graph; a.total = B * H;
   FETA_REQUIRE(x && u && lam && coeff && n_real && dx && dcoeff && dbias_part && cat, "spec_filter_cat_bwd: null pointer");
   FETA_REQUIRE(feta_spec_cat_bwd_supported(N, H, dh, P, K, heads_share_graph),
-               "spec_filter_cat_bwd: needs 4 heads x 16, order 4, N <= 64, K <= 32 (multiple of 4), every head on the graph");
+               "spec_filter_cat_bwd: needs 4 heads x 16 or 8 heads x 8, order 4, N <= 64, K <= 32 (multiple of 4), every head on the graph");
   int rc = check_filter(a, dh, x, dx);
   if (rc != FETA_OK) return rc;
   FETA_REQUIRE(cat->dout && cat->y2 && cat->filt && cat->w_cat && cat->dxn && cat->partial,
@@ -2295,7 +2355,9 @@ extern "C" int feta_spec_filter_cat_fwd_coeff(const float* x, int64_t x_sb, int6
   a.B = B; a.N = N; a.H = H; a.P = P; a.K = K; a.share = heads_share_graph; a.total = B * H;
   FETA_REQUIRE(x && u && lam && coeff && n_real && y && cat, "spec_filter_cat_fwd: null pointer");
   FETA_REQUIRE(feta_spec_cat_supported(N, H, dh, P, K, heads_share_graph),
-               "spec_filter_cat_fwd: needs 4 heads x 16, order 4, N <= 128, K <= 32 (multiple of 4), every head on the graph");
+               "spec_filter_cat_fwd: needs 4 heads x 16 (N <= 128) or 8 heads x 8 (N <= 64), order 4, K <= 32 (multiple of 4), every head "
+               "on the graph");
+  FETA_REQUIRE(cr == nullptr || H == 4, "spec_filter_cat_fwd_coeff: the role is 4 heads x 16 only (H=%d: use feta_spec_filter_cat_fwd)", H);
   int rc = check_filter(a, dh, x, y);
   if (rc != FETA_OK) return rc;
   FETA_REQUIRE(cat->y2 && cat->w_cat && cat->out, "spec_filter_cat_fwd: y2, w_cat, out");

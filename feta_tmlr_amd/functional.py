@@ -128,9 +128,10 @@ class FilterCoefficientsFn(torch.autograd.Function):
         if pending is not None:
             pending.coeff_fwd_req = None
             pending.coeff_dsum_req = pending.coeff_dsum_out = None
-            if USE_COEFF_DSUM and pending.coeff_armed and n <= 64 and h * b <= COEFF_ROLE_MAX_BLOCKS:
+            if USE_COEFF_DSUM and pending.coeff_armed and n <= 64 and h == 4 and h * b <= COEFF_ROLE_MAX_BLOCKS:
                 # this node's backward will run: the filter stage's forward launch, which comes next and leaves most of the
-                # chip idle, may compute the tanh part of it (A, Bm: feta_coeff_dsum) - PendingSums.coeff_dsum_role
+                # chip idle, may compute the tanh part of it (A, Bm: feta_coeff_dsum) - PendingSums.coeff_dsum_role.  4 heads
+                # only: the launch that carries the role (feta_spec_filter_cat_fwd_coeff) has no 8-head form
                 pending.coeff_dsum_req = (cj.detach(), n_real, s.detach(), gb.detach(), b, n, h)
         ctx.save_for_backward(cj, n_real, s, gb)
         ctx.dims = (b, n, h, gcn_weight.shape[0])

@@ -219,8 +219,10 @@ int feta_spec_filter_bwd(const float* x, int64_t x_sb, int64_t x_sn,
  * transformer/models.py:223-224: output = linear_cat(cat(output, allout_filtered)).  With W_cat = [Wa | Wb] ([64][128]):
  *   out = xn Wa^T + filt Wb^T + b_cat,  filt = U Ytil + bias  =>  filt Wb^T = U (Ytil Wb^T) + bias Wb^T
  * - the filter half is a [K x 64] x [64 x 64] product in the eigen domain, the stack half the graph's own rows through a
- * 64 x 64 product: both are done by the workgroup that filters the graph (feta_spec_cat_supported: 4 heads x 16, order 4,
- * N <= 128, K <= 32, every head on the graph).  y (= filt) is still written (linear_cat's backward contracts it).
+ * 64 x 64 product: both are done by the workgroup that filters the graph.  feta_spec_cat_supported: two shapes of d = 64 -
+ * 4 heads x 16 with N <= 128, or 8 heads x 8 with N <= 64 (a wave's 16-column tile then holds heads 2t and 2t + 1 and its
+ * W_k tile is block-diagonal; coeff is [H*B][P*8*8] and bias [8] as for feta_spec_filter_fwd at dh = 8) -, order 4, K <= 32
+ * (a multiple of 4), every head on the graph, fp32.  y (= filt) is still written (linear_cat's backward contracts it).
  * y2: the stack output rows [N*B][64], row(b, i) = b*y2_sb + i*y2_sn elements; seen through its last BatchNorm when
  * y2_stats (fresh partial sums [Gx + 1][2][64]: finalized here over M rows - workgroup 0 publishes bn_out [4][64] and
  * updates rmean / rvar / nbt, as feta_rowlin_fwd_ex does for its x operand) or y2_bn (a published block) is given, else
@@ -251,7 +253,8 @@ int feta_spec_filter_cat_fwd(const float* x, int64_t x_sb, int64_t x_sn, const f
 
 /* The same launch with feta_coeff_dsum (its arguments; N <= 64) in trailing workgroups: the launch runs one workgroup per
  * graph and leaves most of the chip idle at small batches, and the tanh pass of the coefficient generator's backward needs
- * forward data only.  role == NULL: feta_spec_filter_cat_fwd.  y, out and bn_out do not depend on the role.
+ * forward data only.  role == NULL: feta_spec_filter_cat_fwd.  y, out and bn_out do not depend on the role.  4 heads x 16
+ * only: a role with H = 8 is FETA_E_ARG (8-head callers launch feta_spec_filter_cat_fwd and keep feta_coeff_bwd).
  * feta_spec_cat_fwd_coeff_fits(B, N, K, blocks): 1 if `blocks` role blocks fit beside the B main workgroups - the role takes
  * the resident slots the main grid leaves free of its last round and a role workgroup walks at most two blocks; the launch
  * with a role that does not fit is FETA_E_ARG (the caller then keeps feta_coeff_bwd). */
@@ -274,7 +277,9 @@ int feta_spec_filter_cat_fwd_coeff(const float* x, int64_t x_sb, int64_t x_sn, c
  * stack output); gs [R][2][64] = per-workgroup (sum dxn, sum dxn * xhat) for the BatchNorm backward of the stack's last norm
  * (NULL without y2_bn); partial [R][partial_ld] = [dW_cat 64 x 128 | db_cat 64] per workgroup, reduced by the caller's
  * feta_colsum_multi.  R = feta_spec_cat_bwd_rows(B) rows in gs and partial: one per graph up to 512 graphs, beyond that a
- * workgroup walks graphs blockIdx, blockIdx + 512, ... and leaves their sum.  P = 4, 4 heads x 16, N <= 64, K <= 32, fp32, every head on the graph (feta_spec_cat_bwd_supported). */
+ * workgroup walks graphs blockIdx, blockIdx + 512, ... and leaves their sum.  feta_spec_cat_bwd_supported: P = 4, 4 heads x 16
+ * or 8 heads x 8 (dcoeff [H*B][P*8*8], dbias_part [B*8][8]: the layouts of feta_spec_filter_bwd at dh = 8; dxn, gs and partial
+ * keep theirs), N <= 64, K <= 32 (a multiple of 4), fp32, every head on the graph. */
 typedef struct feta_spec_cat_grad {
   const float* dout;
   const float* y2;
