@@ -335,6 +335,23 @@ SIGNATURES.update({
     'feta_encoder_infer_ex': ([C.POINTER(EncoderInferEx), _S], C.c_int),
 })
 
+
+class Gather(C.Structure):
+    """struct feta_gather (include/feta_hip.h) - field order must match the header."""
+    _fields_ = [
+        ('s_x', _F), ('s_degree', _F), ('s_labels', C.c_void_p), ('s_n', _I), ('s_node_off', _I), ('s_pe', _F),
+        ('s_pe_off', _I), ('s_u', _F), ('s_lam', _F), ('s_lap', _F), ('ids', _I),
+        ('G', C.c_int), ('B', C.c_int), ('N', C.c_int), ('F', C.c_int), ('K', C.c_int), ('lap_dim', C.c_int),
+        ('dtype', C.c_int), ('label_kind', C.c_int),
+        ('x', C.c_void_p), ('mask', C.c_void_p), ('degree', _F), ('degree_rows', _F), ('pe', C.c_void_p), ('u', _F),
+        ('lam', _F), ('lap', _F), ('n_real', _I), ('node_off', _I), ('labels', C.c_void_p),
+    ]
+
+
+SIGNATURES['feta_batch_gather'] = ([C.POINTER(Gather), _S], C.c_int)
+
+LABELS_NONE, LABELS_GRAPH_F32, LABELS_GRAPH_I64, LABELS_NODE_I64 = 0, 1, 2, 3      # FETA_LABELS_*
+
 ABI_VERSION = 13
 
 
@@ -1061,6 +1078,17 @@ class Abi:
                         'feta_encoder_fwd_save_sums')
         else:
             self._check(self.lib.feta_encoder_fwd_save(C.byref(d), stream), 'feta_encoder_fwd_save')
+
+    def batch_gather(self, g, b, n, stream, f=0, k=0, lap_dim=0, dtype=0, label_kind=LABELS_NONE, **ptrs):
+        """feta_batch_gather: the padded batch of the graphs ids [b] (int32, on the device) out of a store of g graphs.
+        Tensor-valued keyword arguments become the descriptor's pointers (store arrays s_*, ids, outputs); an output
+        left out is skipped.  dtype: the descriptor's integer (FETA_F32 | FETA_BF16), type of the outputs x and pe."""
+        d = Gather()
+        d.G, d.B, d.N, d.F, d.K, d.lap_dim, d.dtype, d.label_kind = g, b, n, f, k, lap_dim, dtype, label_kind
+        for name, t in ptrs.items():
+            if t is not None:
+                setattr(d, name, t.data_ptr())
+        self._check(self.lib.feta_batch_gather(C.byref(d), stream), 'feta_batch_gather')
 
 
 def bind(cdll):

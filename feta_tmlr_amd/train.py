@@ -101,13 +101,14 @@ def task_loss(task, model, criterion, batch9, graph_cache=None, padded_node_labe
     return criterion(output, labels), output
 
 
-def train_step(task, model, criterion, optimizer, batch9, graph_cache=None, lr=None):
-    """One iteration of the reference's train_epoch loop body.  -> loss (0-d tensor, no sync)."""
+def train_step(task, model, criterion, optimizer, batch9, graph_cache=None, lr=None, padded_node_labels=False):
+    """One iteration of the reference's train_epoch loop body.  -> loss (0-d tensor, no sync).
+    padded_node_labels: as task_loss (batches of transformer.store.DeviceGraphStore.batch carry node labels padded)."""
     if lr is not None:
         for group in optimizer.param_groups:
             group['lr'] = lr
     optimizer.zero_grad(set_to_none=True)
-    loss, _ = task_loss(task, model, criterion, batch9, graph_cache)
+    loss, _ = task_loss(task, model, criterion, batch9, graph_cache, padded_node_labels=padded_node_labels)
     loss.backward()
     optimizer.step()
     from .functional import DropoutState
@@ -253,6 +254,92 @@ class GraphedTrainStep:
         for key, dst in self.cache.extra.items():   # e.g. the per-row degree scale of this batch
             if torch.is_tensor(dst):
                 dst.copy_(graph_cache.extra[key], non_blocking=True)
+        self.graph.replay()
+        if self.drop_calls:
+            from .functional import DropoutState
+            DropoutState.replayed(self.drop_calls)
+        return self.loss
+
+
+class StoreTrainStep(GraphedTrainStep):
+    """GraphedTrainStep fed from a ``transformer.store.DeviceGraphStore``: the captured hipGraph begins with the ONE
+    feta_batch_gather launch that builds the padded batch from ``batch_size`` graph ids in a static device buffer, then
+    runs forward, loss, backward and the optimiser update.  A step is ``step(ids)``: a host sequence costs one copy of
+    4 * batch_size bytes, a device int32 tensor (a slice of a device-side permutation) no host data at all; nothing
+    else is fed - no collate, no eigendecomposition, no copies into static buffers.
+
+    One instance per (bucket n_pad, batch_size); the same snapshot / restore contract, set_lr and DropoutState device
+    mode as GraphedTrainStep (construction does not advance training: the warm-up and capture steps run on
+    ``example_ids``, default the first graphs of the bucket).  Only FULL batches are captured: the ragged last batch of
+    a bucket goes through ``store.batch(ids)`` and ``train_step(..., padded_node_labels=task == 'sbm')``.
+    filter_mode='spectral' only, and train.lap_sign_flip is not applied inside the captured step.
+    dtype: storage type of x and pe as the gather emits them; the task shells embed fp32 x, so they keep float32 (a
+    bf16-storage model rounds its rows and pe itself) and torch.bfloat16 is for a model that consumes bf16 x directly."""
+
+    def __init__(self, task, model, criterion, optimizer, store, n_pad, batch_size, dtype=torch.float32,
+                 example_ids=None, warmup_iters=3):
+        from .transformer.store import GatherBuffers
+        self.task, self.model, self.criterion, self.optimizer = task, model, criterion, optimizer
+        if getattr(model.encoder, 'filter_mode', 'spectral') != 'spectral':
+            raise ValueError("StoreTrainStep runs filter_mode='spectral' models (the store holds no edge list)")
+        self.store = store
+        for group in optimizer.param_groups:
+            if not group.get('capturable', False):
+                raise ValueError('StoreTrainStep needs make_optimizer(..., capturable=True)')
+            if not torch.is_tensor(group['lr']):
+                group['lr'] = torch.tensor(float(group['lr']), device=store.device)
+        self.bufs = GatherBuffers(store, batch_size, n_pad, dtype)
+        self._pinned, self._copied, self._turn = [None, None], [None, None], 0
+        if example_ids is None:
+            members = store.bucket_ids(n_pad)
+            if len(members) == 0:
+                raise ValueError('no graph of the store is padded to %d' % n_pad)
+            example_ids = [int(members[i % len(members)]) for i in range(batch_size)]
+        self._set_ids(example_ids)
+        self.static, self.cache = self.bufs.batch9(), self.bufs.cache()
+        # warm-up and capture as GraphedTrainStep does them (device-resident dropout key, snapshot before, restore after)
+        from .functional import DropoutState
+        DropoutState.begin_device_mode(store.device)
+        snap = self._snapshot()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup_iters):
+                self._body()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.loss = self._body()
+        self._restore(snap)
+
+    def _set_ids(self, ids):
+        import numpy as np
+        ids = self.store.device_ids(ids) if torch.is_tensor(ids) else np.asarray(ids, np.int32)
+        if tuple(ids.shape) != (self.bufs.bsz,):
+            raise ValueError('this step was captured for exactly %d ids, got %s (a ragged batch goes through '
+                             'store.batch and train_step)' % (self.bufs.bsz, tuple(ids.shape)))
+        if torch.is_tensor(ids):
+            self.bufs.ids.copy_(ids, non_blocking=True)
+            return
+        # one asynchronous host-to-device copy, straight into the static buffer, out of one of two pinned buffers used
+        # alternately (BatchStager's scheme: a buffer is refilled only after the copy enqueued from it has been read)
+        turn = self._turn
+        self._turn ^= 1
+        if self._pinned[turn] is None:
+            self._pinned[turn] = torch.empty(self.bufs.bsz, dtype=torch.int32, pin_memory=True)
+            self._copied[turn] = torch.cuda.Event()
+        else:
+            self._copied[turn].synchronize()
+        self._pinned[turn].numpy()[:] = ids
+        self.bufs.ids.copy_(self._pinned[turn], non_blocking=True)
+        self._copied[turn].record()
+
+    def _body(self):
+        self.store.gather_into(self.bufs)
+        return super()._body()
+
+    def __call__(self, ids):
+        self._set_ids(ids)
         self.graph.replay()
         if self.drop_calls:
             from .functional import DropoutState

@@ -988,6 +988,56 @@ int feta_spectral_kernel(const float* u, const float* lam, const int32_t* n_real
                          float beta, int p, float lam_offset, int zero_diag, float* out,
                          int B, int N, int K, feta_stream_t stream);
 
+/* ---- device-resident graph store: one padded batch per launch ----------------------------------------
+ * A split lives on the device as flat per-graph arrays (transformer/store.py: DeviceGraphStore), its spectra computed
+ * once; feta_batch_gather builds the padded batch of the graphs `ids` names - the tensors data.BatchStager.stage and
+ * attach_device_spectrum emit - in ONE launch, so that it can sit inside a captured training step and the host sends
+ * the ids only (replaces GraphDataset_v2.collate_fn, transformer/data.py:161-225, and the pickle cache of
+ * transformer/position_encoding.py:35-49).
+ *   store: graph g owns the rows [s_node_off[g], s_node_off[g] + s_n[g]) of the per-node arrays s_x [sumN,F],
+ *   s_degree [sumN], s_u [sumN,K], s_lap [sumN,lap_dim] (and of s_labels for node labels) and row g of s_lam [G,K];
+ *   its n x n kernel starts at s_pe + s_pe_off[g] with a row pitch of n rounded up to a multiple of 4, the columns
+ *   behind n zero, and s_pe_off[g] a multiple of 4: every row starts on 16 bytes.
+ *   ids [B] int32 ON THE DEVICE.  An id outside [0, G) or a graph with more than N nodes gives an empty graph
+ *   (n_real 0, everything masked, zeros, label 0 / -100) and nothing of the store is read for it.
+ *   outputs: every one may be NULL (skipped; its store array may then be NULL too); EVERY element of the others is
+ *   written, the padding included, so no buffer has to be cleared between replays.
+ * One workgroup per graph and 64-row chunk (grid B x ceil(N / 64)), no LDS.  16-byte loads where the widths (F, N, K,
+ * lap_dim multiples of 4) and the pointers (16-byte aligned; bf16 outputs 8) allow, element-wise otherwise.
+ * x / pe as FETA_BF16: rounded to nearest even from the stored fp32. */
+#define FETA_LABELS_NONE 0
+#define FETA_LABELS_GRAPH_F32 1   /* s_labels float [G]      -> labels float [B] */
+#define FETA_LABELS_GRAPH_I64 2   /* s_labels int64 [G]      -> labels int64 [B] */
+#define FETA_LABELS_NODE_I64 3    /* s_labels int64 [sumN]   -> labels int64 [B,N], -100 on the padded positions */
+typedef struct feta_gather {
+  const float* s_x;            /* [sumN,F] */
+  const float* s_degree;       /* [sumN] */
+  const void* s_labels;        /* label_kind */
+  const int32_t* s_n;          /* [G] node counts */
+  const int64_t* s_node_off;   /* [G] first row of each graph */
+  const float* s_pe;           /* flat, see above */
+  const int64_t* s_pe_off;     /* [G] */
+  const float* s_u;            /* [sumN,K] */
+  const float* s_lam;          /* [G,K] */
+  const float* s_lap;          /* [sumN,lap_dim] */
+  const int32_t* ids;          /* [B], device */
+  int G, B, N, F, K, lap_dim;
+  int dtype;                   /* FETA_F32 | FETA_BF16: storage type of the outputs x and pe [T] */
+  int label_kind;              /* FETA_LABELS_* */
+  void* x;                     /* [B,N,F] [T] */
+  void* mask;                  /* [B,N] bytes, 1 = padding */
+  float* degree;               /* [B,N] */
+  float* degree_rows;          /* [N*B], row = node * B + graph */
+  void* pe;                    /* [B,N,N] [T] */
+  float* u;                    /* [B,N,K] */
+  float* lam;                  /* [B,K] */
+  float* lap;                  /* [B,N,lap_dim] */
+  int32_t* n_real;             /* [B] */
+  int32_t* node_off;           /* [B] exclusive prefix sum of n_real (B * N < 2^24) */
+  void* labels;                /* label_kind */
+} feta_gather;
+int feta_batch_gather(const feta_gather* d, feta_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
