@@ -252,6 +252,31 @@ SIGNATURES.update({
     'feta_ffn_fwd_coeff': ([C.POINTER(Ffn), C.POINTER(CoeffFwdRole), _S], C.c_int),
 })
 
+class LinDw(C.Structure):
+    """struct feta_lin_dw (include/feta_hip.h): the dW role of feta_attn_block_bwd_sums_dw."""
+    _fields_ = [('dy', _F), ('x', _F), ('dw', _F), ('db', _F), ('R', C.c_int), ('K', C.c_int), ('N', C.c_int)]
+
+
+class LinDwReq:
+    """dW / db of the coefficient generator's C x C linear, left by the filter stage's autograd node for the first layer's
+    attention backward to carry (functional.PendingSums.lin_dw_req): dy = dcoeff [R, N], x = pooled [R, K], dw [N, K],
+    db [N].  Detached tensors only."""
+    __slots__ = ('dy', 'x', 'dw', 'db')
+
+    def __init__(self, dy, x, dw, db):
+        self.dy, self.x, self.dw, self.db = dy.detach(), x.detach(), dw.detach(), db.detach()
+
+    def shape(self):
+        return self.dy.shape[0], self.x.shape[1], self.dy.shape[1]      # R, K, N
+
+    def run(self, abi, stream):
+        """nobody carried it: the library product and a column-sum launch, as without the deferral"""
+        from . import _lib
+        with _lib.tuned_gemm():
+            torch.mm(self.dy.t(), self.x, out=self.dw)
+        abi.colsum_multi([(self.dy, self.db)], stream)
+
+
 class AttnBlockGrad(C.Structure):
     """struct feta_attn_block_grad (include/feta_hip.h) - field order must match the header."""
     _fields_ = [
@@ -269,6 +294,10 @@ SIGNATURES.update({
     'feta_attn_block_bwd_blocks': ([C.c_int], C.c_int),
     'feta_attn_block_bwd': ([C.POINTER(AttnBlockGrad), _S], C.c_int),
     'feta_attn_block_bwd_sums': ([C.POINTER(AttnBlockGrad), C.POINTER(ColsumSeg), C.c_int, _S], C.c_int),
+    'feta_attn_block_bwd_dw_slots': ([C.c_int] * 3, C.c_int),
+    'feta_attn_block_bwd_dw_tiles': ([C.c_int] * 2, C.c_int),
+    'feta_attn_block_bwd_dw_supported': ([C.c_int] * 6, C.c_int),
+    'feta_attn_block_bwd_sums_dw': ([C.POINTER(AttnBlockGrad), C.POINTER(ColsumSeg), C.c_int, C.POINTER(LinDw), _S], C.c_int),
 })
 
 
@@ -813,9 +842,10 @@ class Abi:
         return int(self.lib.feta_attn_block_bwd_blocks(b))
 
     def attn_block_bwd(self, b, n, scale, stream, seq_first=True, Gs=0, partial_ld=0, partial_ptr=None, sums=(), ln_eps=1e-5,
-                       heads=4, **ptrs):
+                       heads=4, lin_dw=None, **ptrs):
         """feta_attn_block_bwd; tensor-valued keyword arguments become the descriptor's pointers.  sums: [(in [R, C],
-        out [C])] column sums that ride in trailing workgroups of the launch (feta_attn_block_bwd_sums)"""
+        out [C])] column sums that ride in trailing workgroups of the launch (feta_attn_block_bwd_sums); lin_dw: a
+        LinDwReq (or any object with dy, x, dw, db and shape()) whose product rides there too (feta_attn_block_bwd_sums_dw)"""
         d = AttnBlockGrad()
         d.B, d.N, d.M, d.scale, d.Gs, d.partial_ld, d.ln_eps, d.H = b, n, b * n, scale, Gs, partial_ld, ln_eps, heads
         d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
@@ -826,11 +856,27 @@ class Abi:
         for k, t in ptrs.items():
             if t is not None:
                 setattr(d, k, t.data_ptr())
-        if sums:
+        if lin_dw is not None:
+            r, k, no = lin_dw.shape()
+            w = LinDw(_p(lin_dw.dy), _p(lin_dw.x), _p(lin_dw.dw), _p(lin_dw.db), r, k, no)
+            self._check(self.lib.feta_attn_block_bwd_sums_dw(C.byref(d), self._colsum_segs(sums), len(sums), C.byref(w), stream),
+                        'feta_attn_block_bwd_sums_dw')
+        elif sums:
             self._check(self.lib.feta_attn_block_bwd_sums(C.byref(d), self._colsum_segs(sums), len(sums), stream),
                         'feta_attn_block_bwd_sums')
         else:
             self._check(self.lib.feta_attn_block_bwd(C.byref(d), stream), 'feta_attn_block_bwd')
+
+    def attn_block_bwd_dw_slots(self, b, n, heads):
+        """workgroup slots the attention-backward launch for b graphs leaves free for the dW role (0: none)"""
+        return int(self.lib.feta_attn_block_bwd_dw_slots(b, n, heads))
+
+    def attn_block_bwd_dw_tiles(self, k, n_out):
+        """tiles of the dW role for a [n_out, k] weight gradient (0: not a tiled shape)"""
+        return int(self.lib.feta_attn_block_bwd_dw_tiles(k, n_out))
+
+    def attn_block_bwd_dw_supported(self, b, n, heads, r, k, n_out):
+        return bool(self.lib.feta_attn_block_bwd_dw_supported(b, n, heads, r, k, n_out))
 
     def ffn_supported(self, d_model, ff):
         return bool(self.lib.feta_ffn_supported(d_model, ff))

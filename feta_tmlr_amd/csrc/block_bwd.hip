@@ -31,6 +31,7 @@
 
 #include "feta_abi_common.h"
 #include "feta_colsum.h"
+#include "feta_lin_dw.h"
 #include "feta_ln.h"
 #include "feta_lp.h"
 #include "feta_rowops.h"
@@ -82,14 +83,30 @@ __device__ __forceinline__ void acc_to(float* p, float v, bool first) {
 // operands) are zeroed in the lane groups of the other head (g >> 1 != sh), operands whose lane is an output column (the
 // K, Q, dO B operands) in the other head's columns (lq >> 3 != sh) - so dq / dk / dv of both heads land in their own
 // columns of the one tile, and delta is head-local because dO already is.  A compile-time flag.
-template <class T, int NT, bool SPLIT, bool LOOP, bool TWO>
-__global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, ColsumPlan sums, int main_grid) {
+// DW: the launch also carries the dW role of the coefficient generator's linear (feta_lin_dw.h) - instantiations of their
+// own, for one workgroup per graph (neither SPLIT nor LOOP) and fp32 storage: the launch the first layer of a stack runs.
+// The role's registers (182 against 74 at NT = 1) belong to those alone: every DW = false instantiation takes an empty
+// argument and compiles to what it was, so a launch that carries no role runs the kernel it always ran.
+static_assert(kDwThreads == kBbThreads, "the dW role is written for the workgroup size of attn_block_bwd_kernel");
+
+template <class T, int NT, bool SPLIT, bool LOOP, bool TWO, bool DW = false>
+__global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, ColsumPlan sums, int main_grid, LinDwHost<DW> dw) {
+  static_assert(!DW || (std::is_same<T, float>::value && !SPLIT && !LOOP), "the dW role: fp32, one workgroup per graph");
   // Workgroups beyond main_grid reduce column sums (feta_colsum.h): the LAST launch of a stack's backward runs one workgroup
   // per graph - half the chip at the BASELINE batch - while every split-K partial of the layers behind it, and of this
   // layer's feed-forward half, is already complete; reduced here, the stack's final reduction launch is left with this
-  // launch's own columns (40 MB -> 8.5 MB at the BASELINE batch)
+  // launch's own columns (40 MB -> 8.5 MB at the BASELINE batch).  In front of them, where the caller asked for it, the
+  // workgroups of the dW role (the long pole of the trailing work: dispatched first).
   if ((int)blockIdx.x >= main_grid) {
-    colsum_role<kBbThreads>(sums, (int)blockIdx.x - main_grid);
+    int rb = (int)blockIdx.x - main_grid;
+    if constexpr (DW) {
+      if (rb < dw.p.wgs) {
+        lin_dw_role(dw.p, rb);
+        return;
+      }
+      rb -= dw.p.wgs;
+    }
+    colsum_role<kBbThreads>(sums, rb);
     return;
   }
   typedef Lp<T> L;
@@ -846,8 +863,67 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
   FETA_RT_LAUNCH_DONE(feta_bbwd_launch);
 }
 
+// Resident workgroups of the carrying instantiation (CUs x workgroups per CU, both asked of the runtime) at the dynamic LDS a
+// launch with the dW role requests: the larger of the role's tiles and the main body's worst case for this NT, so that the
+// answer depends on the instantiation only.  0: unknown, no role.
+template <int NT, bool TWO>
+size_t block_bwd_dw_lds() {
+  size_t lds = block_bwd_lds_bytes<float>(NT, true, false, TWO ? 2 * kBbH : kBbH);   // (BatchNorm or LayerNorm, never both)
+  const size_t lds_ln = block_bwd_lds_bytes<float>(NT, false, true, TWO ? 2 * kBbH : kBbH);
+  if (lds < lds_ln) lds = lds_ln;
+  if (lds < (size_t)lin_dw_lds_bytes()) lds = lin_dw_lds_bytes();
+  if (lds < sizeof(float) * colsum_role_lds_floats(kBbThreads)) lds = sizeof(float) * colsum_role_lds_floats(kBbThreads);
+  return lds;
+}
+template <int NT, bool TWO>
+int block_bwd_dw_slots() {
+  // per instantiation and device ordinal (as LdsSeen); the first call on a device - the predicate's - comes before any
+  // capture.  Two threads racing here store the same value.
+  static std::atomic<int> slots[kMaxDevices];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  int have = slots[dev].load(std::memory_order_acquire);
+  if (have == 0) {
+    const size_t lds = block_bwd_dw_lds<NT, TWO>();
+    auto kern = attn_block_bwd_kernel<float, NT, false, false, TWO, true>;
+    static LdsSeen lds_seen;
+    allow_dynamic_lds(kern, lds, lds_seen);
+    int cus = 0, per = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, kBbThreads, lds) != hipSuccess || cus < 1 || per < 1) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    have = cus * per;
+    slots[dev].store(have, std::memory_order_release);
+  }
+  return have;
+}
+static int block_bwd_dw_slots_of(int N, int heads) {
+  const bool two = heads == 8;
+  switch ((N + 15) / 16) {
+    case 1: return two ? block_bwd_dw_slots<1, true>() : block_bwd_dw_slots<1, false>();
+    case 2: return two ? block_bwd_dw_slots<2, true>() : block_bwd_dw_slots<2, false>();
+    case 3: return two ? block_bwd_dw_slots<3, true>() : block_bwd_dw_slots<3, false>();
+    default: return two ? block_bwd_dw_slots<4, true>() : block_bwd_dw_slots<4, false>();
+  }
+}
+// Role workgroups for `tiles` dW tiles beside `grid` main workgroups: what the main grid leaves free of ONE round (every
+// main workgroup is resident from the start, as it is without the role), a multiple of 8 where there are that many (the
+// XCD-aware tile order).  FETA_LIN_DW_WGS=n: n role workgroups whatever is free (A/B timing, tests).  0: no room.
+static int block_bwd_dw_wgs(int slots, int grid, int tiles) {
+  if (const char* e = getenv("FETA_LIN_DW_WGS")) if (atoi(e) > 0) return atoi(e) < tiles ? atoi(e) : tiles;
+  int free_slots = slots - grid;
+  if (free_slots < 1) return 0;
+  if (free_slots > tiles) free_slots = tiles;
+  return free_slots >= 8 ? (free_slots & ~7) : free_slots;
+}
+
 template <class T, int NT, bool TWO = false>
-int launch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
+int launch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, const feta_lin_dw* dw, hipStream_t stream) {
   size_t lds = block_bwd_lds_bytes<T>(NT, a.bn1 != nullptr, a.ln1_gamma != nullptr, TWO ? 2 * kBbH : kBbH);
   const int grid = feta_attn_block_bwd_blocks(a.B);
   ColsumPlan plan{};
@@ -857,38 +933,57 @@ int launch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hi
     auto kern = attn_block_bwd_kernel<T, NT, true, false, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
-    hipLaunchKernelGGL(kern, dim3(2 * a.B + tiles), dim3(kBbThreads), lds, stream, a, plan, 2 * a.B);
+    hipLaunchKernelGGL(kern, dim3(2 * a.B + tiles), dim3(kBbThreads), lds, stream, a, plan, 2 * a.B, LinDwHost<false>{});
   } else if (grid == a.B) {
+    if constexpr (std::is_same<T, float>::value) {
+      if (dw != nullptr) {   // the instantiation with the dW role
+        LinDwHost<true> host{};
+        LinDwPlan& p = host.p;
+        p.dy = dw->dy; p.x = dw->x; p.dw = dw->dw; p.db = dw->db;
+        p.R = dw->R; p.K = dw->K; p.N = dw->N;
+        p.tj = dw->K / kDwJ;
+        p.tiles = lin_dw_tiles(dw->K, dw->N);
+        p.wgs = block_bwd_dw_wgs(block_bwd_dw_slots<NT, TWO>(), grid, p.tiles);
+        FETA_REQUIRE(p.wgs > 0, "attn_block_bwd_sums_dw: %d graphs leave no workgroup slot free (feta_attn_block_bwd_dw_supported)", a.B);
+        lds = block_bwd_dw_lds<NT, TWO>();
+        auto kern = attn_block_bwd_kernel<float, NT, false, false, TWO, true>;
+        static LdsSeen lds_seen;
+        allow_dynamic_lds(kern, lds, lds_seen);
+        hipLaunchKernelGGL(kern, dim3(grid + p.wgs + tiles), dim3(kBbThreads), lds, stream, a, plan, grid, host);
+        return check_launch("feta_attn_block_bwd_sums_dw");
+      }
+    }
     auto kern = attn_block_bwd_kernel<T, NT, false, false, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
-    hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid);
+    hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid, LinDwHost<false>{});
   } else {
     auto kern = attn_block_bwd_kernel<T, NT, false, true, TWO>;
     static LdsSeen lds_seen;
     allow_dynamic_lds(kern, lds, lds_seen);
-    hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid);
+    hipLaunchKernelGGL(kern, dim3(grid + tiles), dim3(kBbThreads), lds, stream, a, plan, grid, LinDwHost<false>{});
   }
   return check_launch("feta_attn_block_bwd");
 }
 
 template <class T>
-int dispatch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
+int dispatch_block_bwd(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, const feta_lin_dw* dw, hipStream_t stream) {
   switch ((a.N + 15) / 16) {
-    case 1: return launch_block_bwd<T, 1>(a, segs, nseg, stream);
-    case 2: return launch_block_bwd<T, 2>(a, segs, nseg, stream);
-    case 3: return launch_block_bwd<T, 3>(a, segs, nseg, stream);
-    default: return launch_block_bwd<T, 4>(a, segs, nseg, stream);
+    case 1: return launch_block_bwd<T, 1>(a, segs, nseg, dw, stream);
+    case 2: return launch_block_bwd<T, 2>(a, segs, nseg, dw, stream);
+    case 3: return launch_block_bwd<T, 3>(a, segs, nseg, dw, stream);
+    default: return launch_block_bwd<T, 4>(a, segs, nseg, dw, stream);
   }
 }
 
 // 8 heads (d_h = 8): fp32 storage only
-static int dispatch_block_bwd_two(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, hipStream_t stream) {
+static int dispatch_block_bwd_two(const BwdArgs& a, const feta_colsum_seg* segs, int nseg, const feta_lin_dw* dw,
+                                  hipStream_t stream) {
   switch ((a.N + 15) / 16) {
-    case 1: return launch_block_bwd<float, 1, true>(a, segs, nseg, stream);
-    case 2: return launch_block_bwd<float, 2, true>(a, segs, nseg, stream);
-    case 3: return launch_block_bwd<float, 3, true>(a, segs, nseg, stream);
-    default: return launch_block_bwd<float, 4, true>(a, segs, nseg, stream);
+    case 1: return launch_block_bwd<float, 1, true>(a, segs, nseg, dw, stream);
+    case 2: return launch_block_bwd<float, 2, true>(a, segs, nseg, dw, stream);
+    case 3: return launch_block_bwd<float, 3, true>(a, segs, nseg, dw, stream);
+    default: return launch_block_bwd<float, 4, true>(a, segs, nseg, dw, stream);
   }
 }
 
@@ -920,7 +1015,41 @@ extern "C" int feta_attn_block_bwd(const feta_attn_block_grad* d, feta_stream_t 
 
 extern "C" int feta_attn_block_bwd_sums(const feta_attn_block_grad* d, const feta_colsum_seg* segs, int nseg,
                                         feta_stream_t stream) {
+  return feta_attn_block_bwd_sums_dw(d, segs, nseg, nullptr, stream);
+}
+
+/* free workgroup slots beside the B main workgroups of the launch that would carry the role: 0 where no instantiation
+ * carries it (more graphs than workgroups: the LOOP form) or the residency is unknown */
+extern "C" int feta_attn_block_bwd_dw_slots(int B, int N, int heads) {
+  if (!feta_attn_block_bwd_supported(N, kBbD, heads) || B < 1 || feta_attn_block_bwd_blocks(B) != B) return 0;
+  const int free_slots = block_bwd_dw_slots_of(N, heads) - B;
+  return free_slots > 0 ? free_slots : 0;
+}
+
+/* tiles of the role for a [N_out, K] weight gradient (0: the shape is not tiled) */
+extern "C" int feta_attn_block_bwd_dw_tiles(int K, int N_out) {
+  return (K >= kDwJ && K % kDwJ == 0 && N_out >= kDwI && N_out % kDwI == 0) ? lin_dw_tiles(K, N_out) : 0;
+}
+
+extern "C" int feta_attn_block_bwd_dw_supported(int B, int N, int heads, int R, int K, int N_out) {
+  return (lin_dw_shape_ok(R, K, N_out) && feta_attn_block_bwd_dw_slots(B, N, heads) > 0) ? 1 : 0;
+}
+
+extern "C" int feta_attn_block_bwd_sums_dw(const feta_attn_block_grad* d, const feta_colsum_seg* segs, int nseg,
+                                           const feta_lin_dw* dw, feta_stream_t stream) {
   FETA_REQUIRE(d != nullptr, "attn_block_bwd: null descriptor");
+  if (dw != nullptr) {
+    FETA_REQUIRE(dw->dy && dw->x && dw->dw, "attn_block_bwd_sums_dw: null pointer");
+    FETA_REQUIRE(lin_dw_shape_ok(dw->R, dw->K, dw->N),
+                 "attn_block_bwd_sums_dw: need R %% %d == 0, K %% %d == 0, N %% %d == 0 (R=%d K=%d N=%d)", kDwK, kDwJ, kDwI,
+                 dw->R, dw->K, dw->N);
+    FETA_REQUIRE(aligned16(dw->dy) && aligned16(dw->x) && aligned16(dw->dw),
+                 "attn_block_bwd_sums_dw: dy, x and dw must be 16-byte aligned");
+    FETA_REQUIRE(d->dtype == FETA_F32, "attn_block_bwd_sums_dw: the role rides in fp32-storage launches only");
+    FETA_REQUIRE(d->dx_b == nullptr, "attn_block_bwd_sums_dw: the two-workgroup form (dx_b) does not carry the role");
+    FETA_REQUIRE(d->B > 0 && feta_attn_block_bwd_blocks(d->B) == d->B,
+                 "attn_block_bwd_sums_dw: the role needs one workgroup per graph (B=%d)", d->B);
+  }
   FETA_REQUIRE(nseg >= 0 && nseg <= FETA_COLSUM_MAX_SEGS && (nseg == 0 || segs != nullptr),
                "attn_block_bwd: 0..%d column-sum segments", FETA_COLSUM_MAX_SEGS);
   for (int i = 0; i < nseg; ++i) FETA_REQUIRE(colsum_seg_ok(segs[i]), "attn_block_bwd: bad segment %d", i);
@@ -944,8 +1073,8 @@ extern "C" int feta_attn_block_bwd_sums(const feta_attn_block_grad* d, const fet
   FETA_REQUIRE(a.H == 0 || a.H == 4 || a.H == 8, "attn_block_bwd: H=%d (0 = 4, 4 or 8 heads)", a.H);
   if (a.H == 8) {
     FETA_REQUIRE(a.dtype == FETA_F32, "attn_block_bwd: 8 heads need fp32 storage");
-    return dispatch_block_bwd_two(a, segs, nseg, (hipStream_t)stream);
+    return dispatch_block_bwd_two(a, segs, nseg, dw, (hipStream_t)stream);
   }
-  if (a.dtype == FETA_BF16) return dispatch_block_bwd<bf16_t>(a, segs, nseg, (hipStream_t)stream);
-  return dispatch_block_bwd<float>(a, segs, nseg, (hipStream_t)stream);
+  if (a.dtype == FETA_BF16) return dispatch_block_bwd<bf16_t>(a, segs, nseg, nullptr, (hipStream_t)stream);
+  return dispatch_block_bwd<float>(a, segs, nseg, dw, (hipStream_t)stream);
 }

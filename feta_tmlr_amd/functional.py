@@ -7,7 +7,7 @@ produced in place: no transposes, no gathers, no scatter into zero-initialised b
 import torch
 
 from . import _lib
-from ._abi import CoeffSavedReq
+from ._abi import CoeffSavedReq, LinDwReq
 
 
 def _token_view(t, batch_first, heads):
@@ -292,6 +292,24 @@ COEFF_ROLE_MAX_BLOCKS = int(_os.environ.get('FETA_COEFF_ROLE_MAX', 2048))
 USE_COEFF_DSUM = _os.environ.get('FETA_COEFF_DSUM', '1') != '0'
 
 
+# dW / db of the coefficient generator's C x C linear as a role of the first layer's attention backward - the stack's last
+# launch, which leaves half the chip idle at the headline batch - instead of a library GEMM launch of its own
+# (feta_attn_block_bwd_sums_dw, csrc/feta_lin_dw.h).  FETA_LIN_DW_ROLE: 0 off; 1 the default policy (the tiles fit the
+# workgroup slots that launch leaves free in ONE round, and the batch is at most LIN_DW_ROLE_MAX_B graphs); 2 wherever the
+# launch can carry it (tests: the role at the smallest shape it takes).  Read at every backward.
+# Measured at the headline shape (C = 1024, N_pad = 37, role on against off, ms per step): B = 64 0.2173 -> 0.2121, B = 96
+# 0.2408 -> 0.2310, B = 128 0.2523 -> 0.2476 (EXPERIMENTS.md); B = 32 takes csrc/lin.hip, not the library.  Nothing beyond 128
+# graphs has been measured - at C = 1024 the 128 tiles no longer fit one round there anyway - so the default stops there.
+LIN_DW_ROLE_MAX_B = 128
+
+
+def lin_dw_role_mode():
+    try:
+        return int(_os.environ.get('FETA_LIN_DW_ROLE', '1'))
+    except ValueError:
+        return 1
+
+
 class PendingSums:
     """Column sums (split-K partial buffer -> gradient) that one backward node of the filter stage leaves for a LATER
     node of the same backward pass which has a launch to carry them (trailing workgroups of feta_lin_bwd, or the
@@ -324,6 +342,38 @@ class PendingSums:
         # launch has taken it (detached tensors only: this object is reachable from the autograd nodes of the stage)
         self.coeff_dsum_req = None
         self.coeff_dsum_out = None
+        # ... and dW / db of the generator's C x C linear: lin_dw_req = an _abi.LinDwReq (detached tensors only) left by
+        # FilterFromPooledFn.backward for the first layer's attention backward (fused_stack: the stack's last launch) -
+        # or, if that backward has no such launch, for the library at the start of the stack's backward
+        self.lin_dw_req = None
+
+    def lin_dw_wanted(self, abi, b, n, heads, r, k, n_out):
+        """May FilterFromPooledFn.backward leave dW / db of the [n_out, k] linear (r rows) to the stack's backward for b
+        graphs of n nodes?  (the stack asks the launch's own predicate again before it carries the request)"""
+        mode = lin_dw_role_mode()
+        if mode == 0 or not (self.stack_armed and not self.stack_done) or self.lin_dw_req is not None:
+            return False
+        if not abi.attn_block_bwd_dw_supported(b, n, heads, r, k, n_out):
+            return False
+        if mode >= 2:
+            return True
+        return b <= LIN_DW_ROLE_MAX_B and abi.attn_block_bwd_dw_tiles(k, n_out) <= abi.attn_block_bwd_dw_slots(b, n, heads)
+
+    def defer_lin_dw(self, req, owners):
+        self.lin_dw_req = req
+        self.owners += [(p_, g_.detach()) for p_, g_ in owners if p_ is not None and g_ is not None]
+        self._queue_finish()
+
+    def take_lin_dw(self):
+        req, self.lin_dw_req = self.lin_dw_req, None
+        return req
+
+    def _queue_finish(self):
+        if not self._callback_queued:
+            # safety net: whatever no later node took (autograd pruned it from this pass) is run when the backward
+            # pass ends
+            torch.autograd.Variable._execution_engine.queue_callback(self._finish_pass)
+            self._callback_queued = True
 
     def coeff_dsum_role(self, abi, graphs, k_eig):
         """Called by the forward that launches feta_spec_filter_cat_fwd for `graphs` graphs on k_eig eigenvectors: -> the
@@ -366,11 +416,7 @@ class PendingSums:
         for p, g in owners:
             if p is not None and g is not None:
                 self.owners.append((p, g.detach()))
-        if not self._callback_queued:
-            # safety net: whatever no later node took (autograd pruned it from this pass) is reduced when the
-            # backward pass ends
-            torch.autograd.Variable._execution_engine.queue_callback(self._finish_pass)
-            self._callback_queued = True
+        self._queue_finish()
 
     def take(self):
         items, self.items = self.items, []
@@ -402,6 +448,9 @@ class PendingSums:
 
     def _finish_pass(self):
         self._callback_queued = False
+        dw_req = self.take_lin_dw()
+        if dw_req is not None:      # (nobody took it: the stack's node was pruned from this pass)
+            dw_req.run(*_lib.backend(dw_req.dy))
         req = self.take_coeff_bwd()
         items = self.take()
         if items:
@@ -479,6 +528,7 @@ class FilterFromPooledFn(torch.autograd.Function):
         b, n, h, dh = x.shape
         xs = _dense_like(x, batch_first)
         # fp32 master precision (also what a regulariser sees)
+        lin_w_in = lin_w      # (the parameter itself: PendingSums.untouched looks at its .grad and hooks)
         pooled, lin_w = pooled.contiguous(), lin_w.contiguous()
         r_, k_, n_ = pooled.shape[0], pooled.shape[1], lin_w.shape[0]
         # csrc/lin.hip (one 16 x 16 tile per wave straight from L2, gradient products and column sums in one launch)
@@ -504,6 +554,7 @@ class FilterFromPooledFn(torch.autograd.Function):
         # pooled's gradient flows into FilterCoefficientsFn: if that node flushes, it runs after this one
         ctx.defer = pending is not None and pending.coeff_armed and ctx.needs_input_grad[1] and not ctx.own_gemm
         ctx.params = (lin_b, bias)
+        ctx.lin_w_param = lin_w_in
         if pending is not None and any(ctx.needs_input_grad):
             pending.armed = True
         # bf16 storage path: the per-block weights the filter kernel reads are bf16 copies of them
@@ -589,8 +640,22 @@ class FilterFromPooledFn(torch.autograd.Function):
             dw_lin = torch.empty_like(lin_w)
             abi.lin_bwd(pooled, lin_w, dcoeff, dpooled, dw_lin, db_lin, stream, pairs=sums, bf16=ctx.gemm_bf16)
         else:
-            sums.append((dcoeff, db_lin))
-            if ctx.defer and PendingSums.untouched(*ctx.params):
+            # dW_lin and db_lin as a role of the stack's last launch (PendingSums.lin_dw_req): only the dX product runs here
+            dw_req = None
+            pend = ctx.pending
+            if (pend is not None and not ctx.lib_bf16 and dcoeff.dtype == torch.float32 and pooled.dtype == torch.float32
+                    and lin_w.dtype == torch.float32 and ctx.params[0] is not None
+                    and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
+                    and pend.lin_dw_wanted(abi, b, n, h, dcoeff.shape[0], pooled.shape[1], dcoeff.shape[1])
+                    and PendingSums.untouched(ctx.lin_w_param, ctx.params[0])):
+                dw_lin = torch.empty_like(lin_w)
+                dw_req = LinDwReq(dcoeff, pooled, dw_lin, db_lin)
+                pend.defer_lin_dw(dw_req, [(ctx.lin_w_param, dw_lin), (ctx.params[0], db_lin)])
+            else:
+                sums.append((dcoeff, db_lin))
+            if not sums:
+                pass
+            elif ctx.defer and PendingSums.untouched(*ctx.params):
                 for pr in sums:
                     ctx.pending.add(*pr)
                 # (dbias is None when only the coefficients were used downstream - a regulariser on them, dy is None)
@@ -603,6 +668,9 @@ class FilterFromPooledFn(torch.autograd.Function):
                 d16 = dcoeff.to(torch.bfloat16)
                 dpooled = torch.mm(d16, w16, out_dtype=torch.float32)
                 dw_lin = torch.mm(d16.t(), p16, out_dtype=torch.float32)
+            elif dw_req is not None:
+                with _lib.tuned_gemm():
+                    dpooled = dcoeff.mm(lin_w)
             else:
                 with _lib.tuned_gemm():
                     dpooled, dw_lin = dcoeff.mm(lin_w), dcoeff.t().mm(pooled)

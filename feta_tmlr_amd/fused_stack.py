@@ -429,6 +429,9 @@ class FusedEncoderStackFn(torch.autograd.Function):
         # reduction at the end (instead of one reduction launch per linear)
         part_f, part_a, tf, ta, wslot = _partial_buffers(abi, new, m, b, n, d, heads, ff0, nl, fused_attn)
         coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
+        # dW / db of the coefficient generator's linear, left by the filter stage for this backward's LAST launch
+        lin_dw = _lin_dw_request(ctx, abi, stream, lambda rq: fused_attn and dt == torch.float32 and
+                                 abi.attn_block_bwd_dw_supported(b, n, heads, *rq.shape()))
         total = tf + ta
         # ONE flat gradient buffer for the whole stack: [weights and biases (reduced partials) | dgamma,
         # dbeta of norm1 / norm2 of every layer]; every parameter gradient returned below is a view of it,
@@ -519,7 +522,7 @@ class FusedEncoderStackFn(torch.autograd.Function):
                                    w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
                                    dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
                                    attn_stats=s['ast'], x0=s['x0'], bn0=s['prm0'] if li > 0 else None, dx=dx0,
-                                   sum_out=gs_prev, sums=early)
+                                   sum_out=gs_prev, sums=early, lin_dw=(lin_dw if li == 0 else None))
                 Gs_next = 2 * GB
                 if gs_prev is not None:
                     gs_prev, Gs_next = _cap_partials(abi, stream, gs_prev, new)
@@ -737,6 +740,7 @@ class FusedLayerNormStackFn(torch.autograd.Function):
             abi, new, m, b, n, d, heads, ff0, nl, fused_attn, ln_f=ffn_on_load,
             ffn_fused=bool(ffn_on_load or (USE_FFN_BWD and abi.ffn_bwd_supported(d, ff0))))
         coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
+        _lin_dw_request(ctx, abi, stream, None)      # (no launch of this backward carries it: the library, here)
         total = tf + ta
         lnw = 2 if ffn_on_load else 4               # LayerNorm partial columns per layer that come from feta_layernorm_bwd
         ln_part = new(GL, nl * lnw * d)
@@ -995,6 +999,7 @@ def _ln_on_load_backward(ctx, d_final, d_concat_last):
     ff0 = params[6].shape[0]
     part_f, part_a, tf, ta, wslot = _partial_buffers(abi, new, m, b, n, d, heads, ff0, nl, True, ln_cols=True, ffn_fused=True)
     coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
+    _lin_dw_request(ctx, abi, stream, None)      # (no launch of this backward carries it: the library, here)
     total = tf + ta
     dwdb_all = new(total)      # [feed-forward slots | attention slots], each followed by its LayerNorm's [dgamma | dbeta]
     slots, ln_slots = {}, {}
@@ -1077,6 +1082,19 @@ def _coeff_bwd_request(ctx, abi, stream, d, ff_last):
         cj, n_real, s, gb, dpooled, partial, b, n, h = req
         abi.coeff_bwd(cj, n_real, s, gb, dpooled, partial, None, None, b, n, h, stream)
         req = None
+    return req
+
+
+def _lin_dw_request(ctx, abi, stream, carries):
+    """dW / db of the coefficient generator's C x C linear (functional.PendingSums.lin_dw_req, an _abi.LinDwReq): -> the
+    request if this backward's last launch - the first layer's feta_attn_block_bwd - will carry it (carries(req)), else
+    None after running it with the library and a column-sum launch, as the filter stage's node would have."""
+    req = ctx.pending.take_lin_dw() if ctx.pending is not None else None
+    if req is None:
+        return None
+    if carries is None or not carries(req):
+        req.run(abi, stream)
+        return None
     return req
 
 

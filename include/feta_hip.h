@@ -654,6 +654,33 @@ int feta_attn_block_bwd(const feta_attn_block_grad* d, feta_stream_t stream);
  * of a stack's backward leaves half the chip idle at the BASELINE batch while the split-K partials of everything behind it
  * are complete - reduced here, the final reduction launch is left with this launch's own partial columns. */
 int feta_attn_block_bwd_sums(const feta_attn_block_grad* d, const feta_colsum_seg* segs, int nseg, feta_stream_t stream);
+/* ... and, in front of them, the "dW" product of the coefficient generator's C x C linear as a role of the same launch
+ * (additive, ABI 13): dw[n][k] = sum_r dy[r][n] x[r][k], db[n] = sum_r dy[r][n] (db nullable), exact fp32 MFMA with the
+ * contraction index ascending - deterministic and independent of the grid.  512-thread workgroups on 128 x 64 tiles of dw,
+ * dispatched behind the main workgroups and before the column-sum tiles; as many as the main grid leaves free of one round
+ * of resident workgroups (CUs x occupancy of the instantiation), each walking several tiles where there are more tiles.
+ * Carried by the one-workgroup-per-graph fp32 launches only (4 or 8 heads): dx_b (two workgroups per graph), bf16 storage
+ * and more graphs than feta_attn_block_bwd_blocks(B) are rejected, as are R % 64, K % 64, N % 128 != 0, null or misaligned
+ * (16 bytes) dy / x / dw.  Everything the main workgroups write is bit-identical with and without the role.  dw == NULL:
+ * feta_attn_block_bwd_sums.
+ *   feta_attn_block_bwd_dw_slots(B, N, heads): workgroup slots the launch for B graphs of N nodes leaves free (0: none, or
+ *        no carrying instantiation);
+ *   feta_attn_block_bwd_dw_tiles(K, N_out): tiles of the role for a [N_out, K] result (0: not a tiled shape) - with no more
+ *        tiles than free slots the role takes one round;
+ *   feta_attn_block_bwd_dw_supported(B, N, heads, R, K, N_out): the shape is tiled AND at least one slot is free.
+ * The role has instantiations of its own (<..., DW = true>): a launch with dw == NULL runs the kernel it ran before. */
+typedef struct feta_lin_dw {
+  const float* dy; /* [R][N] gradient of the linear's output */
+  const float* x;  /* [R][K] its input */
+  float* dw;       /* [N][K] */
+  float* db;       /* [N], nullable */
+  int R, K, N;
+} feta_lin_dw;
+int feta_attn_block_bwd_dw_slots(int B, int N, int heads);
+int feta_attn_block_bwd_dw_tiles(int K, int N_out);
+int feta_attn_block_bwd_dw_supported(int B, int N, int heads, int R, int K, int N_out);
+int feta_attn_block_bwd_sums_dw(const feta_attn_block_grad* d, const feta_colsum_seg* segs, int nseg, const feta_lin_dw* dw,
+                                feta_stream_t stream);
 
 /* ---- feed-forward half of one encoder layer in ONE launch -----------------------------------
  * x = BN1(y1) (x_bn | x_stats as in feta_rowlin_ex / feta_attn_block);  h = relu(x W1^T + b1);
