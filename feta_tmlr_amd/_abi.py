@@ -392,6 +392,13 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _fill(desc, ptrs):
+    """tensor-valued keyword arguments become the descriptor's pointers; None leaves the field null"""
+    for k, t in ptrs.items():
+        if t is not None:
+            setattr(desc, k, t.data_ptr())
+
+
 def _same_dtype(dtype, *tensors):
     for t in tensors:
         if t is not None and t.dtype != dtype:
@@ -455,38 +462,24 @@ class Abi:
         sb, sn = tok_strides(q)
         assert tok_strides(k) == (sb, sn) and tok_strides(v) == (sb, sn)
         osb, osn = tok_strides(out)
+        bf = 1 if q.dtype == torch.bfloat16 else 0
+        dropping = drop is not None and drop[0] > 0.0
+        plain = not (clamp5 or dropping or bf)      # feta_attn_fwd itself: fp32, exp(s - rowmax), no dropout
+        if not plain:
+            _same_dtype(q.dtype, k, v, pe, out, attn)
         if clamp5:
             assert drop is None or drop[0] == 0.0, 'clamp5 with attention dropout is not instantiated'
-            _same_dtype(q.dtype, k, v, pe, out, attn)
-            self._check(self.lib.feta_attn_fwd_stab(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), osb, osn,
-                                                    _p(attn), _p(stats), scale, 1, 1 if q.dtype == torch.bfloat16 else 0,
-                                                    b, n, h, dh, stream), 'feta_attn_fwd_stab')
-            return
-        if drop is not None and drop[0] > 0.0 and torch.is_tensor(drop[1]):
+            name, mid = 'feta_attn_fwd_stab', (1, bf)
+        elif dropping and torch.is_tensor(drop[1]):
             # device-resident key (functional.DropoutState in device mode): drop = (p, state int64[2], offset_add)
-            _same_dtype(q.dtype, k, v, pe, out, attn)
             assert drop[1].dtype == torch.int64 and drop[1].numel() == 2 and drop[1].device == q.device
-            self._check(self.lib.feta_attn_fwd_drop_dev(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), osb, osn,
-                                                        _p(attn), _p(stats), scale, float(drop[0]), _p(drop[1]),
-                                                        int(drop[2]), 1 if q.dtype == torch.bfloat16 else 0, b, n, h, dh,
-                                                        stream), 'feta_attn_fwd_drop_dev')
-            return
-        if drop is not None and drop[0] > 0.0:
-            _same_dtype(q.dtype, k, v, pe, out, attn)
-            self._check(self.lib.feta_attn_fwd_drop(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), osb, osn,
-                                                    _p(attn), _p(stats), scale, float(drop[0]), int(drop[1]), int(drop[2]),
-                                                    1 if q.dtype == torch.bfloat16 else 0, b, n, h, dh, stream),
-                        'feta_attn_fwd_drop')
-            return
-        if q.dtype == torch.bfloat16:
-            _same_dtype(torch.bfloat16, k, v, pe, out, attn)
-            self._check(self.lib.feta_attn_fwd_bf16(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real),
-                                                    _p(out), osb, osn, _p(attn), _p(stats), scale,
-                                                    b, n, h, dh, stream), 'feta_attn_fwd_bf16')
-            return
-        self._check(self.lib.feta_attn_fwd(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real),
-                                           _p(out), osb, osn, _p(attn), _p(stats), scale,
-                                           b, n, h, dh, stream), 'feta_attn_fwd')
+            name, mid = 'feta_attn_fwd_drop_dev', (float(drop[0]), _p(drop[1]), int(drop[2]), bf)
+        elif dropping:
+            name, mid = 'feta_attn_fwd_drop', (float(drop[0]), int(drop[1]), int(drop[2]), bf)
+        else:
+            name, mid = ('feta_attn_fwd' if plain else 'feta_attn_fwd_bf16'), ()
+        self._check(getattr(self.lib, name)(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), osb, osn, _p(attn),
+                                            _p(stats), scale, *mid, b, n, h, dh, stream), name)
 
     @staticmethod
     def attn_bwd_takes_dout2(n, dh, dtype=torch.float32, heads=None):
@@ -505,44 +498,27 @@ class Abi:
             assert tok_strides(t) == (sb, sn)
         osb, osn = tok_strides(out)
         assert tok_strides(dout) == (osb, osn)
+        bf = 1 if q.dtype == torch.bfloat16 else 0
+        dropping = drop is not None and drop[0] > 0.0
+        plain = not (clamp5 or dropping or bf)      # feta_attn_bwd itself: fp32, exp(s - rowmax), no dropout
+        # (only the plain entry point takes a second gradient into out_each_head)
+        second = (_p(dout2),)
+        if not plain:
+            _same_dtype(q.dtype, k, v, pe, out, dout, dq, dk, dv)
+            assert dout2 is None
+            second = ()
         if clamp5:
-            assert dout2 is None and (drop is None or drop[0] == 0.0)
-            _same_dtype(q.dtype, k, v, pe, out, dout, dq, dk, dv)
-            self._check(self.lib.feta_attn_bwd_stab(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), _p(dout),
-                                                    osb, osn, _p(stats), _p(delta), _p(dq), _p(dk), _p(dv), scale, 1,
-                                                    1 if q.dtype == torch.bfloat16 else 0, b, n, h, dh, stream),
-                        'feta_attn_bwd_stab')
-            return
-        if drop is not None and drop[0] > 0.0 and torch.is_tensor(drop[1]):
-            _same_dtype(q.dtype, k, v, pe, out, dout, dq, dk, dv)
-            assert dout2 is None
-            self._check(self.lib.feta_attn_bwd_drop_dev(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), _p(dout),
-                                                        osb, osn, _p(stats), _p(delta), _p(dq), _p(dk), _p(dv), scale,
-                                                        float(drop[0]), _p(drop[1]), int(drop[2]),
-                                                        1 if q.dtype == torch.bfloat16 else 0, b, n, h, dh, stream),
-                        'feta_attn_bwd_drop_dev')
-            return
-        if drop is not None and drop[0] > 0.0:
-            _same_dtype(q.dtype, k, v, pe, out, dout, dq, dk, dv)
-            assert dout2 is None
-            self._check(self.lib.feta_attn_bwd_drop(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), _p(dout),
-                                                    osb, osn, _p(stats), _p(delta), _p(dq), _p(dk), _p(dv), scale,
-                                                    float(drop[0]), int(drop[1]), int(drop[2]),
-                                                    1 if q.dtype == torch.bfloat16 else 0, b, n, h, dh, stream),
-                        'feta_attn_bwd_drop')
-            return
-        if q.dtype == torch.bfloat16:
-            _same_dtype(torch.bfloat16, k, v, pe, out, dout, dq, dk, dv)
-            assert dout2 is None
-            self._check(self.lib.feta_attn_bwd_bf16(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real),
-                                                    _p(out), _p(dout), osb, osn, _p(stats), _p(delta),
-                                                    _p(dq), _p(dk), _p(dv), scale, b, n, h, dh, stream),
-                        'feta_attn_bwd_bf16')
-            return
-        self._check(self.lib.feta_attn_bwd(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real),
-                                           _p(out), _p(dout), _p(dout2), osb, osn, _p(stats), _p(delta),
-                                           _p(dq), _p(dk), _p(dv), scale, b, n, h, dh, stream),
-                    'feta_attn_bwd')
+            assert drop is None or drop[0] == 0.0
+            name, mid = 'feta_attn_bwd_stab', (1, bf)
+        elif dropping and torch.is_tensor(drop[1]):
+            name, mid = 'feta_attn_bwd_drop_dev', (float(drop[0]), _p(drop[1]), int(drop[2]), bf)
+        elif dropping:
+            name, mid = 'feta_attn_bwd_drop', (float(drop[0]), int(drop[1]), int(drop[2]), bf)
+        else:
+            name, mid = ('feta_attn_bwd' if plain else 'feta_attn_bwd_bf16'), ()
+        self._check(getattr(self.lib, name)(_p(q), _p(k), _p(v), sb, sn, _p(pe), _p(n_real), _p(out), _p(dout), *second,
+                                            osb, osn, _p(stats), _p(delta), _p(dq), _p(dk), _p(dv), scale, *mid,
+                                            b, n, h, dh, stream), name)
 
     def coeff_fwd(self, attn, n_real, s, gcn_bias, cj, pooled, stream):
         b, h, n, _ = attn.shape
@@ -775,9 +751,7 @@ class Abi:
         d.x_split = x_split
         if partial_ptr is not None:
             d.partial = partial_ptr
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         return d
 
     def rowlin_fwd_ex(self, desc, stream):
@@ -806,9 +780,7 @@ class Abi:
         d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
         d.momentum, d.eps, d.Gx, d.tie_qk = momentum, eps, Gx, int(tie_qk)
         d.dtype = _stack_dtype(ptrs, ('x', 'pe', 'qkv', 'out', 'y'))
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         return d
 
     def attn_block_launch(self, desc, stream, sums=()):
@@ -853,9 +825,7 @@ class Abi:
             d.partial = partial_ptr
         d.dtype = _stack_dtype(ptrs, ('dy', 'y1', 'qkv', 'out', 'dout2', 'pe', 'x0', 'dx', 'dx_b'), f32_ok=('dout2',))
         d.dout2_f32 = int(ptrs.get('dout2') is not None and ptrs['dout2'].dtype == torch.float32)
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         if lin_dw is not None:
             r, k, no = lin_dw.shape()
             w = LinDw(_p(lin_dw.dy), _p(lin_dw.x), _p(lin_dw.dw), _p(lin_dw.db), r, k, no)
@@ -896,9 +866,7 @@ class Abi:
         d.y_f32 = int(ptrs['y'].dtype == torch.float32)
         if ptrs.get('y_ln_out') is not None:
             d.y_ln_f32 = int(ptrs['y_ln_out'].dtype == torch.float32)
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         return d
 
     def ffn_launch(self, desc, stream, coeff=None):
@@ -930,9 +898,7 @@ class Abi:
         d.g_f32 = int(ptrs['dy'].dtype == torch.float32)
         if ptrs.get('g_y') is not None and ptrs['g_y'].dtype != ptrs['dy'].dtype:
             raise TypeError('dy and g_y must share a dtype')
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         return d
 
     def ffn_bwd_launch(self, desc, stream, coeff=None):
@@ -981,18 +947,20 @@ class Abi:
         return self.lib.feta_layernorm_blocks(m)
 
     @staticmethod
-    def _dt(t):
-        if t.dtype == torch.float32:
+    def _dt_of(dtype, what=''):
+        """FETA_F32 | FETA_BF16 of a torch dtype; what: the operands it belongs to, for the error text (' rows')"""
+        if dtype == torch.float32:
             return 0
-        if t.dtype == torch.bfloat16:
+        if dtype == torch.bfloat16:
             return 1
-        raise TypeError('float32 or bfloat16 rows, got %s' % t.dtype)
+        raise TypeError('float32 or bfloat16%s, got %s' % (what, dtype))
 
     def layernorm_fwd(self, y, gamma, beta, eps, out, stats, stream):
         """y, out: float32 or bfloat16 rows (independently: feta_layernorm_fwd_ex)"""
         m, d = y.shape
         self._check(self.lib.feta_layernorm_fwd_ex(_p(y), _p(gamma), _p(beta), eps, _p(out), _p(stats), m, d,
-                                                   self._dt(y), self._dt(out), stream), 'feta_layernorm_fwd')
+                                                   self._dt_of(y.dtype, ' rows'), self._dt_of(out.dtype, ' rows'), stream),
+                    'feta_layernorm_fwd')
 
     def layernorm_bwd(self, dout, y, stats, gamma, dy, partial, dgdb, stream, partial_ld=0, partial_ptr=None, eps=1e-5):
         """partial_ptr / partial_ld: this LayerNorm's columns inside a shared [blocks, total] partial buffer
@@ -1001,7 +969,8 @@ class Abi:
         m, d = y.shape
         pp = _p(partial) if partial_ptr is None else C.c_void_p(partial_ptr)
         self._check(self.lib.feta_layernorm_bwd_eps(_p(dout), _p(y), _p(stats), eps, _p(gamma), _p(dy), pp, partial_ld,
-                                                    _p(dgdb), m, d, self._dt(dout), self._dt(y), self._dt(dy), stream),
+                                                    _p(dgdb), m, d, self._dt_of(dout.dtype, ' rows'),
+                                                    self._dt_of(y.dtype, ' rows'), self._dt_of(dy.dtype, ' rows'), stream),
                     'feta_layernorm_bwd')
 
     def eigh_sym_supported(self, n):
@@ -1038,42 +1007,34 @@ class Abi:
                     setattr(e, k, v)
         return table
 
+    def _encoder_desc(self, cls, b, n, heads, ff, layers, layer_norm, seq_first):
+        """the header the one-launch encoder descriptors share -> (descriptor, the layer table it points to: keep it
+        alive until the launch has been issued)"""
+        table = self._encoder_table(layers)
+        d = cls()
+        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
+        d.norm = 1 if layer_norm else 0
+        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d.layers = C.cast(table, C.c_void_p)
+        return d, table
+
     def encoder_infer(self, b, n, heads, ff, layers, layer_norm, stream, seq_first=True, **ptrs):
         """feta_encoder_infer (ABI 12): the whole stack's forward for inference in one launch.  layers: one dict per
         layer - tensors for the pointer fields of feta_encoder_layer, n1_eps / n2_eps / tie_qk as numbers;
         tensor-valued keyword arguments (x, pe, n_real, rowscale, y, out, attn) become the descriptor's pointers."""
-        table = self._encoder_table(layers)
-        d = EncoderInfer()
-        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
-        d.norm = 1 if layer_norm else 0
-        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d, table = self._encoder_desc(EncoderInfer, b, n, heads, ff, layers, layer_norm, seq_first)
         _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k != 'n_real'))
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
-        d.layers = C.cast(table, C.c_void_p)
+        _fill(d, ptrs)
         self._check(self.lib.feta_encoder_infer(C.byref(d), stream), 'feta_encoder_infer')
 
     def encoder_infer_ex_supported(self, n, d_model, heads, ff, nl, dtype=torch.float32):
         return bool(self.lib.feta_encoder_infer_ex_supported(n, d_model, heads, ff, nl, self._dt_of(dtype)))
 
-    @staticmethod
-    def _dt_of(dtype):
-        if dtype == torch.float32:
-            return 0
-        if dtype == torch.bfloat16:
-            return 1
-        raise TypeError('float32 or bfloat16, got %s' % dtype)
-
     def encoder_infer_ex(self, b, n, heads, ff, layers, layer_norm, stream, dtype=torch.float32, seq_first=True, **ptrs):
         """feta_encoder_infer_ex: encoder_infer with a tile / compute type `dtype` (torch.float32: the fp32 kernel, bit for
         bit; torch.bfloat16: bf16 tiles and bf16 MFMAs, 4 heads).  x and pe are float32 or - with dtype bfloat16 -
         bfloat16 tensors of ONE type (the descriptor's in_dtype); everything else is float32, the outputs included."""
-        table = self._encoder_table(layers)
-        d = EncoderInferEx()
-        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
-        d.norm = 1 if layer_norm else 0
-        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d, table = self._encoder_desc(EncoderInferEx, b, n, heads, ff, layers, layer_norm, seq_first)
         d.dtype = self._dt_of(dtype)
         x, pe = ptrs.get('x'), ptrs.get('pe')
         if x is None:
@@ -1082,10 +1043,7 @@ class Abi:
             raise TypeError('x is %s, pe is %s: one in_dtype for both' % (x.dtype, pe.dtype))
         d.in_dtype = self._dt_of(x.dtype)
         _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k not in ('n_real', 'x', 'pe')))
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
-        d.layers = C.cast(table, C.c_void_p)
+        _fill(d, ptrs)
         self._check(self.lib.feta_encoder_infer_ex(C.byref(d), stream), 'feta_encoder_infer_ex')
 
     def encoder_fwd_save_supported(self, n, d_model, heads, ff, nl, dtype=torch.float32, tie_qk=False):
@@ -1100,25 +1058,18 @@ class Abi:
         the saved tensors qkv, out_save, attn_stats, y1, h, y2, each [L, ...] (contiguous per layer: the layer stride is
         the tensor's stride(0)) or, L = 1, without the leading axis.  sums: [(in [R, C], out [C])] column sums that
         ride in trailing workgroups of the launch."""
-        table = self._encoder_table(layers)
-        d = EncoderFwdSave()
-        d.B, d.N, d.H, d.FF, d.L = b, n, heads, ff, len(layers)
-        d.norm = 1 if layer_norm else 0
-        d.row_sb, d.row_sn = (1, b) if seq_first else (n, 1)
+        d, table = self._encoder_desc(EncoderFwdSave, b, n, heads, ff, layers, layer_norm, seq_first)
         d.dtype = d.in_dtype = self._dt_of(dtype)
         tok = ('x', 'pe', 'qkv', 'out_save', 'y1', 'h', 'y2')
         _same_dtype(dtype, *(ptrs.get(k) for k in tok))
         _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k not in tok + ('n_real',)))
-        for k, t in ptrs.items():
-            if t is not None:
-                setattr(d, k, t.data_ptr())
+        _fill(d, ptrs)
         for k in self.SAVE_KINDS:
             t = ptrs.get(k)
             if t is not None and len(layers) > 1:
                 if t.shape[0] != len(layers) or not t[0].is_contiguous():
                     raise ValueError('feta_encoder_fwd_save: %s must be [L, ...] with contiguous layers' % k)
                 setattr(d, k + '_stride' if k != 'out_save' else 'out_stride', t.stride(0))
-        d.layers = C.cast(table, C.c_void_p)
         if sums:
             self._check(self.lib.feta_encoder_fwd_save_sums(C.byref(d), self._colsum_segs(sums), len(sums), stream),
                         'feta_encoder_fwd_save_sums')
@@ -1131,9 +1082,7 @@ class Abi:
         left out is skipped.  dtype: the descriptor's integer (FETA_F32 | FETA_BF16), type of the outputs x and pe."""
         d = Gather()
         d.G, d.B, d.N, d.F, d.K, d.lap_dim, d.dtype, d.label_kind = g, b, n, f, k, lap_dim, dtype, label_kind
-        for name, t in ptrs.items():
-            if t is not None:
-                setattr(d, name, t.data_ptr())
+        _fill(d, ptrs)
         self._check(self.lib.feta_batch_gather(C.byref(d), stream), 'feta_batch_gather')
 
 

@@ -1,6 +1,10 @@
 """The whole stack of DiffTransformerEncoderLayers as ONE autograd node with a hand-scheduled forward
 and backward over the C ABI: FusedEncoderStackFn (BatchNorm layers, described here) and
-FusedLayerNormStackFn (LayerNorm layers, described at the class).
+FusedLayerNormStackFn (LayerNorm layers, described at the class and at _ln_on_load_forward).  The two nodes and the three
+LayerNorm forward forms hold the per-layer schedules only; what they share exists once: the per-call geometry (_Geom,
+on ctx.geom), the forward and backward prologues and epilogues (_begin_* / _finish_*), the attention half's allocations
+(_attn_alloc), the launch sequences without the fused kernels (_attn_fwd_unfused, _ffn_bwd_unfused, _attn_bwd_unfused)
+and the flat gradient buffer with its slot allocator (_GradSlots).
 
 Per layer, forward (5 launches):
     F1  qkv  = BN2_prev(y2_prev) W_in^T                       feta_rowlin_fwd_ex (finalizes BN2_prev)
@@ -114,11 +118,10 @@ def ln_one_launch_supported(abi, layers, n, b, d_model, tie, dt):
     return abi.encoder_fwd_save_supported(n, d_model, heads, ff, len(layers), dt, tie)
 
 
-def ln_on_load_supported(abi, layers, n, b, d_model, tie):
-    """every launch of the stack is one of the four fused kernels (they carry the LayerNorm on load)"""
-    if not (USE_LN_ON_LOAD and USE_ATTN_BLOCK and USE_FFN_FUSED and USE_FFN_BWD and USE_ATTN_BLOCK_BWD) or tie:
+def _fused_kernels_take(abi, layers, n, b, d_model, heads):
+    """every launch of the stack is one of the four fused kernels (csrc/block.hip, ffn.hip, ffn_bwd.hip, block_bwd.hip)"""
+    if not (USE_ATTN_BLOCK and USE_FFN_FUSED and USE_FFN_BWD and USE_ATTN_BLOCK_BWD):
         return False
-    heads = layers[0].self_attn.num_heads
     if not (abi.attn_block_supported(n, d_model, heads) and abi.attn_block_bwd_supported(n, d_model, heads)
             and abi.attn_block_bwd_blocks(b) > 0):
         return False
@@ -126,23 +129,23 @@ def ln_on_load_supported(abi, layers, n, b, d_model, tie):
                for l in layers)
 
 
+def ln_on_load_supported(abi, layers, n, b, d_model, tie):
+    """the four fused kernels carry the LayerNorm on load: every launch of the stack has to be one of them"""
+    if not USE_LN_ON_LOAD or tie:
+        return False
+    return _fused_kernels_take(abi, layers, n, b, d_model, layers[0].self_attn.num_heads)
+
+
 def lowp_stack_supported(abi, layers, n, b, d_model):
     """bf16 storage (layers.set_storage_dtype): the stack runs iff every launch of it is one of the four fused kernels
-    (csrc/block.hip, ffn.hip, ffn_bwd.hip, block_bwd.hip - the ones instantiated for bf16 tiles - and, LayerNorm stacks,
-    feta_layernorm_*_ex)."""
-    if not (USE_ATTN_BLOCK and USE_FFN_FUSED and USE_FFN_BWD and USE_ATTN_BLOCK_BWD):
-        return False
+    (the ones instantiated for bf16 tiles - and, LayerNorm stacks, feta_layernorm_*_ex)."""
     l0 = layers[0]
     heads = l0.self_attn.num_heads
     if heads != 4:   # the 8-head form of the block kernels (ABI 13) is instantiated for fp32 storage only
         return False
     if l0.self_attn.tie_qk or (not l0.batch_norm and not USE_LN_STACK):
         return False
-    if not (abi.attn_block_supported(n, d_model, heads) and abi.attn_block_bwd_supported(n, d_model, heads)
-            and abi.attn_block_bwd_blocks(b) > 0):
-        return False
-    return all(abi.ffn_supported(d_model, l.linear1.out_features) and abi.ffn_bwd_supported(d_model, l.linear1.out_features)
-               for l in layers)
+    return _fused_kernels_take(abi, layers, n, b, d_model, heads)
 
 
 def stack_supported(layers, d_model):
@@ -204,47 +207,6 @@ def _cap_partials(abi, stream, st, new, shift_row=False):
     return tot, 1
 
 
-def _partial_buffers(abi, new, m, b, n, d, heads, ff0, nl, fused_attn, ln_cols=False, ln_f=None, ln_a=None, ffn_fused=None):
-    """Split-K partial buffers of a stack backward and the slot allocator.  Two buffers, because their row counts
-    differ: 'f' (linear2 / linear1 of every layer) has one row per feta_rowlin_chunks(M) row chunk, 'a' (out_proj /
-    in_proj) the same or - with the fused attention-block backward - one row per graph.  dwdb_all = [f columns |
-    a columns | norm tail] is the flat gradient buffer every parameter gradient is a view of; ONE multi-segment
-    reduction fills it at the end of backward.  -> (part_f, part_a, tf, ta, wslot)"""
-    rc = abi.rowlin_chunks(m)
-    ra = abi.attn_block_bwd_blocks(b) if fused_attn else rc
-    # the fused feed-forward backward chooses its own split-K chunk count (feta_ffn_bwd_chunks: the row-wise kernels' chunks
-    # or, where that keeps its grid within one round of resident workgroups, half as many)
-    if ffn_fused is None:
-        ffn_fused = USE_FFN_BWD and abi.ffn_bwd_supported(d, ff0)
-    if ffn_fused:
-        rc = abi.ffn_bwd_chunks(m, ff0)
-    # ln_cols (LayerNorm on load): every layer's slot is followed by [dgamma | dbeta] of the LayerNorm whose backward
-    # the kernel applies on its gradient load (norm2 behind the feed-forward slot, norm1 behind the attention slot)
-    ln_f = ln_cols if ln_f is None else ln_f
-    ln_a = ln_cols if ln_a is None else ln_a
-    tf = nl * ((ff0 * d + ff0) + (d * ff0 + d) + (2 * d if ln_f else 0))
-    ta = nl * ((d * d + d) + (3 * d * d + 3 * d) + (2 * d if ln_a else 0))
-    part_f, part_a = new(rc, tf), new(ra, ta)
-    cur = {'f': 0, 'a': 0}
-
-    def wslot(kind, no, ki):
-        """-> (pointer to this linear's partial columns, its offset in dwdb_all)"""
-        off = cur[kind]
-        cur[kind] += no * ki + no
-        buf, base = (part_f, 0) if kind == 'f' else (part_a, tf)
-        return buf.data_ptr() + 4 * off, base + off
-
-    def raw(kind, count):
-        """-> offset in dwdb_all of `count` further columns of this kind (they follow the previous slot in the row)"""
-        off = cur[kind]
-        cur[kind] += count
-        return (0 if kind == 'f' else tf) + off
-
-    wslot.cur = cur
-    wslot.raw = raw
-    return part_f, part_a, tf, ta, wslot
-
-
 class StackTail:
     """Hand-over between the BatchNorm stack and the ONE consumer of its output when that consumer is linear_cat
     (transformer/models.py:223-224): the last BatchNorm is then never materialised either.  The stack returns the
@@ -259,55 +221,301 @@ class StackTail:
         self.G2 = 0
 
 
-class FusedEncoderStackFn(torch.autograd.Function):
+class _Geom:
+    """Geometry of one stack call, its two allocators and the operands every launch shares.  The forward builds it
+    (_begin_forward) and leaves it on ctx; the backward binds it to its own stream (_begin_backward)."""
 
-    @staticmethod
-    def forward(ctx, src, pe, degree_rows, n_real, layers, need_attn, tail, pending, *params):
-        abi, stream = _lib.backend(src, pe, n_real)
-        ctx.set_materialize_grads(False)   # no zero tensor for the (non-differentiable) attn output
-        if len(layers):
-            STACK_FLAT_GRAD.pop(layers[0], None)   # the buffer of an earlier backward is stale from here on
-        n, b, d = src.shape
-        m = n * b
-        nl = len(layers)
-        heads = layers[0].self_attn.num_heads
-        dh = d // heads
-        tie = layers[0].self_attn.tie_qk
-        scale = float(dh) ** -0.5
-        dev = src.device
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    def __init__(self, abi, stream, src, pe, degree_rows, n_real, layers):
+        a0 = layers[0].self_attn
+        self.abi, self.stream = abi, stream
+        self.n, self.b, self.d = src.shape
+        self.m, self.nl = self.n * self.b, len(layers)
+        self.heads, self.tie = a0.num_heads, a0.tie_qk
+        self.dh = self.d // self.heads
+        self.scale = float(self.dh) ** -0.5
         # bf16 storage (layers.set_storage_dtype; BASELINE configs 3 / 5): src and pe arrive as bf16, every token tensor
         # of the stack is bf16 (qkv, out, y1, h, y2 and the gradients in backward), the kernels run their bf16
         # instantiations (include/feta_hip.h: dtype = FETA_BF16).  Statistics, parameter blocks, attn, every parameter
         # gradient: fp32.  What LEAVES the stack is fp32 again - the last layer writes its y2 as fp32 (feta_ffn.y_f32) and
         # its per-head outputs once more as fp32 (feta_attn_block.out_f32) - so the filter stage behind it (coefficient
         # generator, spectral filter, linear_cat with the folded BatchNorm) runs unchanged and there is no cast launch.
-        dt = src.dtype
-        lowp = dt != torch.float32
-        newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-        if lowp and (pe is not None and pe.dtype != dt):
-            raise TypeError('bf16 stack: pe must be %s as well' % dt)
-        G = abi.rowlin_blocks(m)
-        x_in = src.contiguous().view(m, d)
-        pe_c = None if pe is None else pe.contiguous()
+        self.dt, self.dev = src.dtype, src.device
+        self.lowp = self.dt != torch.float32
+        self.pe = None if pe is None else pe.contiguous()
+        self.rowscale, self.n_real = degree_rows, n_real
+        self.G = 0      # BatchNorm stacks: row blocks of the row-wise kernels (rows of their statistics and sums)
+
+    def new(self, *s):
+        return torch.empty(s, dtype=torch.float32, device=self.dev)
+
+    def newt(self, *s):
+        """a token tensor: the stack's storage type"""
+        return torch.empty(s, dtype=self.dt, device=self.dev)
+
+
+def _begin_forward(ctx, src, pe, degree_rows, n_real, layers, pending):
+    """-> (geometry, the stack's input rows [M, d])"""
+    abi, stream = _lib.backend(src, pe, n_real)
+    ctx.set_materialize_grads(False)   # no zero tensor for the (non-differentiable) attn output
+    ctx.pending = pending
+    STACK_FLAT_GRAD.pop(layers[0], None)   # the buffer of an earlier backward is stale from here on
+    g = _Geom(abi, stream, src, pe, degree_rows, n_real, layers)
+    if g.lowp and (pe is not None and pe.dtype != g.dt):
+        raise TypeError('bf16 stack: pe must be %s as well' % g.dt)
+    if g.lowp and not lowp_stack_supported(abi, layers, g.n, g.b, g.d):
+        raise NotImplementedError('bf16 storage: the fused stack needs d_model = 64, 4 heads, N <= 64'
+                                  + (', BatchNorm' if layers[0].batch_norm else ''))
+    return g, src.contiguous().view(g.m, g.d)
+
+
+def _attn_alloc(g, li, need_attn):
+    """what the attention half of layer li writes -> (attn, ast, qkv, out, out32, y1); attn only where the caller wants
+    the last layer's, out32 (the per-head outputs once more as fp32) only on the last layer of a bf16 stack"""
+    last = li == g.nl - 1
+    attn = g.new(g.b, g.heads, g.n, g.n) if (need_attn and last) else None
+    ast = g.new(g.b, g.heads, g.n, 2)
+    qkv = g.newt(g.m, 3 * g.d)
+    out = g.newt(g.n, g.b, g.heads, g.dh)
+    out32 = g.new(g.n, g.b, g.heads, g.dh) if (g.lowp and last) else None
+    return attn, ast, qkv, out, out32, g.newt(g.m, g.d)
+
+
+def _fwd_sums(pending, li):
+    """the filter stage's forward column sums ride in the first launch of the stack that has trailing workgroups"""
+    return pending.take_fwd() if (pending is not None and li == 0) else ()
+
+
+def _attn_fwd_unfused(g, li, x, w_in, b_in, w_o, b_o, bufs, pending, bn_in=None, x_bn=None, y_shift=None):
+    """The attention half without csrc/block.hip: F1 in_proj, then F2 + F3 in one launch, one workgroup per (graph, 32
+    query rows) (csrc/attnout.hip), or F2 attention core and F3 out_proj + degree + residual.  BatchNorm stacks pass
+    bn_in (the previous layer's norm2: finalized and applied on in_proj's operand load), x_bn (its parameter block, for
+    the residual) and y_shift (norm1's running mean: the statistics of y1 are wanted)
+    bufs: what _attn_alloc returned  -> (statistics [G1 + 1, 2, d], G1), or (None, 0) without y_shift"""
+    abi, stream, n, b, d, m, heads = g.abi, g.stream, g.n, g.b, g.d, g.m, g.heads
+    attn, ast, qkv, out, _, y1 = bufs
+    dsc = abi.rowlin_ex(m, d, 3 * d, x=x, w=w_in, bias=b_in, y=qkv, **(bn_in or {}))
+    abi.rowlin_fwd_ex(dsc, stream)
+    st1, G1 = None, 0
+    if USE_ATTN_OUT and not g.lowp and abi.attn_out_supported(n, d, heads):
+        if y_shift is not None:
+            G1 = abi.attn_out_stat_rows(b, n)
+            st1 = g.new(G1 + 1, 2, d)      # (+ the shift row: the sums are relative to norm1's running mean)
+        abi.attn_out_fwd(b, n, g.scale, stream, tie_qk=g.tie, x=x, x_bn=x_bn, w_out=w_o, b_out=b_o, pe=g.pe,
+                         n_real=g.n_real, rowscale=g.rowscale, qkv=qkv, out=out, attn_stats=ast, attn=attn, y=y1,
+                         y_stats=st1, y_shift=y_shift, sums=_fwd_sums(pending, li))
+        if st1 is not None:
+            st1, G1 = _cap_partials(abi, stream, st1, g.new, shift_row=True)
+        return st1, G1
+    q, k, v = _views(qkv, n, b, heads, g.dh)
+    if g.tie:
+        k = q
+    abi.attn_fwd(q, k, v, g.pe, g.n_real, out.permute(1, 0, 2, 3), attn, ast, g.scale, stream)
+    if y_shift is not None:
+        G1 = g.G
+        st1 = g.new(G1 + 1, 2, d)
+    dsc = abi.rowlin_ex(m, d, d, x=out.view(m, d), w=w_o, bias=b_o, rowscale=g.rowscale, residual=x, res_bn=x_bn, y=y1,
+                        stats=st1, stats_shift=y_shift)
+    abi.rowlin_fwd_ex(dsc, stream)
+    return st1, G1
+
+
+def _finish_forward(ctx, g, layers, params, saved, final, out32, attn):
+    """records what the backward needs -> the node's outputs (final, concat heads of the last layer, attn)"""
+    ctx.saved_state = saved
+    if CAPTURE_SAVED is not None:
+        CAPTURE_SAVED.append(saved)
+    ctx.geom = g
+    ctx.params = params
+    ctx.eps = [(float(l.norm1.eps), float(l.norm2.eps)) for l in layers]
+    ctx.owner = layers[0]
+    if attn is not None:
+        ctx.mark_non_differentiable(attn)
+    concat_last = (out32 if g.lowp else saved[-1]['out']).view(g.n, g.b, g.d)
+    return final.view(g.n, g.b, g.d), concat_last, attn
+
+
+class _GradSlots:
+    """Split-K partial buffers of a stack backward, the flat gradient buffer and the slot allocator.  Two partial
+    buffers, because their row counts differ: 'f' (linear2 / linear1 of every layer) has one row per
+    feta_rowlin_chunks(M) row chunk, 'a' (out_proj / in_proj) the same or - with the fused attention-block backward -
+    one row per graph.  flat = [f columns | a columns | norm tail] is ONE gradient buffer for the whole stack: every
+    weight / bias gradient goes through the partial buffers and ONE deterministic multi-segment reduction at the end of
+    backward (instead of one reduction launch per linear), the tail holds [tail_rows, d] per layer of dgamma / dbeta
+    that come from elsewhere, and every parameter gradient (`grads`) is a view of it, so a data-parallel trainer
+    all-reduces it in place (parallel.FlatBufferAllReduce)."""
+
+    def __init__(self, g, params, fused_attn, ffn_fused, ln_f=False, ln_a=False, tail_rows=0):
+        abi, d, nl = g.abi, g.d, g.nl
+        ff0 = params[6].shape[0]
+        rc = abi.rowlin_chunks(g.m)
+        ra = abi.attn_block_bwd_blocks(g.b) if fused_attn else rc
+        # the fused feed-forward backward chooses its own split-K chunk count (feta_ffn_bwd_chunks: the row-wise kernels'
+        # chunks or, where that keeps its grid within one round of resident workgroups, half as many)
+        if ffn_fused:
+            rc = abi.ffn_bwd_chunks(g.m, ff0)
+        # ln_f / ln_a (LayerNorm on load): every layer's slot is followed by [dgamma | dbeta] of the LayerNorm whose
+        # backward the kernel applies on its gradient load (norm2 behind the feed-forward slot, norm1 behind the attention slot)
+        self.tf = tf = nl * ((ff0 * d + ff0) + (d * ff0 + d) + (2 * d if ln_f else 0))
+        self.ta = ta = nl * ((d * d + d) + (3 * d * d + 3 * d) + (2 * d if ln_a else 0))
+        self.part_f, self.part_a = g.new(rc, tf), g.new(ra, ta)
+        self.total = tf + ta
+        self.flat = g.new(self.total + nl * tail_rows * d)
+        self.tail = self.flat[self.total:].view(nl, tail_rows, d) if tail_rows else None
+        self.cur = {'f': 0, 'a': 0}
+        self.d, self.params = d, params
+        self.grads = [None] * len(params)
+
+    def _lin(self, idx, kind, no, ki):
+        """the next [no, ki] weight + [no] bias columns of this kind go to parameters idx, idx + 1
+        -> pointer to the linear's partial columns"""
+        off = self.cur[kind]
+        self.cur[kind] += no * ki + no
+        buf, at = (self.part_f, off) if kind == 'f' else (self.part_a, self.tf + off)
+        self.grads[idx] = self.flat[at:at + no * ki].view(no, ki)
+        if self.params[idx + 1] is not None:
+            self.grads[idx + 1] = self.flat[at + no * ki:at + no * ki + no]
+        return buf.data_ptr() + 4 * off
+
+    def _norm(self, idx, kind):
+        """[dgamma | dbeta] of a LayerNorm on load follow the previous slot in the partial rows"""
+        d = self.d
+        at = (0 if kind == 'f' else self.tf) + self.cur[kind]
+        self.cur[kind] += 2 * d
+        self.grads[idx], self.grads[idx + 1] = self.flat[at:at + d], self.flat[at + d:at + 2 * d]
+
+    def ffn(self, li, ff, ln=False):
+        """the feed-forward half of layer li (, norm2 on load) -> partial pointers of linear2, linear1"""
+        base = li * PER_LAYER
+        pp = self._lin(base + 8, 'f', self.d, ff)
+        pp1 = self._lin(base + 6, 'f', ff, self.d)
+        if ln:
+            self._norm(base + 10, 'f')
+        return pp, pp1
+
+    def attn(self, li, ln=False):
+        """the attention half of layer li (, norm1 on load) -> partial pointers of out_proj, in_proj"""
+        base = li * PER_LAYER
+        ppo = self._lin(base + 2, 'a', self.d, self.d)
+        ppi = self._lin(base + 0, 'a', 3 * self.d, self.d)
+        if ln:
+            self._norm(base + 4, 'a')
+        return ppo, ppi
+
+    def norm_tail(self, li, which):
+        """dgamma, dbeta of norm1 (which = 0) / norm2 (1) of layer li in the tail"""
+        dg, db = self.tail[li, 2 * which], self.tail[li, 2 * which + 1]
+        idx = li * PER_LAYER + (10 if which else 4)
+        self.grads[idx], self.grads[idx + 1] = dg, db
+        return dg, db
+
+    def early(self, a_done):
+        """segments that are complete when the first layer's attention backward starts: 'f', and `a_done` columns of 'a'"""
+        segs = [(self.part_f, self.flat[:self.tf])]
+        if a_done > 0:
+            segs.append((self.part_a[:, :a_done], self.flat[self.tf:self.tf + a_done]))
+        return segs
+
+    def rest(self, early_done=None):
+        """segments of the final reduction: everything, or what early(early_done) left"""
+        if early_done is not None:
+            return [(self.part_a[:, early_done:], self.flat[self.tf + early_done:self.total])]
+        return [(self.part_f, self.flat[:self.tf]), (self.part_a, self.flat[self.tf:self.total])]
+
+
+def _begin_backward(ctx, d_final, fused_attn=None, lin_dw_rides=False):
+    """Binds the geometry to this backward, takes what the filter stage left for it and shapes the incoming gradient.
+    fused_attn None: _fused_attn_bwd decides.  lin_dw_rides: the first layer's feta_attn_block_bwd - the LAST launch -
+    carries dW / db of the coefficient generator's linear where the kernel takes it; else the library runs it, here.
+    -> (geometry, fused_attn, coeff_req, lin_dw, gradient rows [M, d] fp32)"""
+    g, params = ctx.geom, ctx.params
+    abi, stream = g.abi, g.stream = _lib.backend(ctx.saved_state[0]['qkv'])
+    if fused_attn is None:
+        fused_attn = _fused_attn_bwd(abi, g.b, g.n, g.d, g.heads, g.tie, g.dt)
+    coeff_req = _coeff_bwd_request(ctx, abi, stream, g.d, params[(g.nl - 1) * PER_LAYER + 6].shape[0])
+    carries = None
+    if lin_dw_rides:
+        carries = lambda rq: (fused_attn and g.dt == torch.float32
+                              and abi.attn_block_bwd_dw_supported(g.b, g.n, g.heads, *rq.shape()))
+    lin_dw = _lin_dw_request(ctx, abi, stream, carries)
+    if d_final is None:   # only the per-head output of the last layer was used
+        d_final = torch.zeros(g.n, g.b, g.d, dtype=torch.float32, device=g.dev)
+    if d_final.dtype != torch.float32:
+        d_final = d_final.float()      # (the stack's output is fp32: so is its gradient)
+    return g, fused_attn, coeff_req, lin_dw, d_final.contiguous().view(g.m, g.d)
+
+
+def _ffn_bwd_unfused(g, s, x, w2, w1, dy, dx1, pp, pp1, tf, load=None, lin1=None):
+    """B1: linear2 backward, then B2: linear1 backward with the residual gradient added in its dX epilogue.  load: what
+    the gradient load applies (BatchNorm stacks: the backward of norm2); lin1: the operand, residual and sum keywords of
+    B2 (BatchNorm stacks: x_bn, add_* through norm2, sum_* for norm1's backward; LayerNorm: add_plain)"""
+    abi, m, d = g.abi, g.m, g.d
+    ff = w1.shape[0]
+    dh_ = g.new(m, ff)
+    dsc = abi.rowlin_ex(m, ff, d, x=s['h'], w=w2, dy=dy, dx=dh_, partial_ptr=pp, partial_ld=tf, **(load or {}))
+    abi.rowlin_bwd_ex(dsc, None, g.stream)
+    dsc = abi.rowlin_ex(m, d, ff, x=x, w=w1, dy=dh_, relu_y=s['h'], dx=dx1, partial_ptr=pp1, partial_ld=tf,
+                        **(lin1 or {}))
+    abi.rowlin_bwd_ex(dsc, None, g.stream)
+
+
+def _attn_bwd_unfused(g, s, w_o, w_in, dy, d2, ppo, ppi, ta, load=None, in_proj=None):
+    """B3: out_proj backward (gradient scaled by degree), B4: attention backward, B5: in_proj backward with the residual
+    gradient in its dX epilogue.  d2: a second gradient into the per-head outputs (the last layer's concat) or None.
+    load / in_proj: as _ffn_bwd_unfused (BatchNorm stacks: norm1's backward on B3's gradient load; x_bn, add_*, and
+    sum_* for the previous layer's norm2 in B5)  -> dx0 [M, d] fp32"""
+    abi, stream, n, b, d, m, heads, dh = g.abi, g.stream, g.n, g.b, g.d, g.m, g.heads, g.dh
+    dconcat = g.new(m, d)
+    dsc = abi.rowlin_ex(m, d, d, x=s['out'].view(m, d), w=w_o, dy=dy, rowscale=g.rowscale, dx=dconcat,
+                        partial_ptr=ppo, partial_ld=ta, **(load or {}))
+    abi.rowlin_bwd_ex(dsc, None, stream)
+    dout2 = None
+    if d2 is not None:
+        if abi.attn_bwd_takes_dout2(n, dh, heads=heads):   # added inside the kernel's loads
+            dout2 = d2.contiguous().view(n, b, heads, dh).permute(1, 0, 2, 3)
+        else:
+            dconcat = dconcat + d2.contiguous().view(m, d)
+    q, k, v = _views(s['qkv'], n, b, heads, dh)
+    if g.tie:
+        k = q
+    dqkv = g.new(m, 3 * d)
+    dq, dk, dv = _views(dqkv, n, b, heads, dh)
+    delta = g.new(b, heads, n)
+    abi.attn_bwd(q, k, v, g.pe, g.n_real, s['out'].permute(1, 0, 2, 3), dconcat.view(n, b, heads, dh).permute(1, 0, 2, 3),
+                 s['ast'], delta, dq, dk, dv, g.scale, stream, dout2=dout2)
+    if g.tie:
+        dqkv[:, :d] += dqkv[:, d:2 * d]
+        dqkv[:, d:2 * d] = 0
+    dx0 = g.new(m, d)
+    dsc = abi.rowlin_ex(m, d, 3 * d, x=s['x0'], w=w_in, dy=dqkv, dx=dx0, partial_ptr=ppi, partial_ld=ta,
+                        **(in_proj or {}))
+    abi.rowlin_bwd_ex(dsc, None, stream)
+    return dx0
+
+
+def _finish_backward(ctx, g, sl, dcur, segments):
+    """ONE reduction launch fills the flat gradient buffer: the given segments and whatever column sums the filter stage
+    left for this launch (functional.PendingSums)  -> the node's gradients"""
+    assert sl.cur == {'f': sl.tf, 'a': sl.ta}
+    g.abi.colsum_multi(segments + _take_pending(ctx), g.stream)
+    STACK_FLAT_GRAD[ctx.owner] = sl.flat
+    return (dcur.view(g.n, g.b, g.d), None, None, None, None, None, None, None) + tuple(sl.grads)
+
+
+class FusedEncoderStackFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, src, pe, degree_rows, n_real, layers, need_attn, tail, pending, *params):
+        g, y_prev = _begin_forward(ctx, src, pe, degree_rows, n_real, layers, pending)
+        abi, stream, new, newt = g.abi, g.stream, g.new, g.newt
+        n, b, d, m, nl, heads = g.n, g.b, g.d, g.m, g.nl, g.heads
+        G = g.G = abi.rowlin_blocks(m)
         block = USE_ATTN_BLOCK and abi.attn_block_supported(n, d, heads)
-        if lowp and not lowp_stack_supported(abi, layers, n, b, d):
-            raise NotImplementedError('bf16 storage: the fused stack needs d_model = 64, 4 heads, N <= 64, BatchNorm')
         saved = []
-        y_prev, st_prev, prm_prev = x_in, None, None
-        attn = None
-        out32 = None
+        st_prev, prm_prev = None, None
         for li, layer in enumerate(layers):
             (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             ff = w1.shape[0]
-            want = need_attn and li == nl - 1
-            attn = new(b, heads, n, n) if want else None
-            ast = new(b, heads, n, 2)
-            qkv = newt(m, 3 * d)
-            out = torch.empty((n, b, heads, dh), dtype=dt, device=dev)
-            if lowp and li == nl - 1:
-                out32 = new(n, b, heads, dh)
-            y1 = newt(m, d)
+            bufs = attn, ast, qkv, out, out32, y1 = _attn_alloc(g, li, need_attn)
             bn_prev = {}
             if li > 0:
                 pl = layers[li - 1].norm2
@@ -321,38 +529,14 @@ class FusedEncoderStackFn(torch.autograd.Function):
                 # F1 + F2 + F3 in one launch, one or two workgroups per graph (csrc/block.hip)
                 G1 = abi.attn_block_stat_rows(b, n)
                 st1 = new(G1 + 1, 2, d)      # (+ the shift row: the sums are relative to norm1's running mean)
-                abi.attn_block_fwd(b, n, scale, stream, heads=heads, tie_qk=tie, x=y_prev, w_in=w_in, b_in=b_in, w_out=w_o,
-                                   b_out=b_o, pe=pe_c, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
+                abi.attn_block_fwd(b, n, g.scale, stream, heads=heads, tie_qk=g.tie, x=y_prev, w_in=w_in, b_in=b_in,
+                                   w_out=w_o, b_out=b_o, pe=g.pe, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
                                    attn_stats=ast, attn=attn, y=y1, y_stats=st1, y_shift=layer.norm1.running_mean,
-                                   out_f32=(out32 if li == nl - 1 else None),
-                                   sums=(pending.take_fwd() if (pending is not None and li == 0) else ()), **bn_prev)
+                                   out_f32=out32, sums=_fwd_sums(pending, li), **bn_prev)
                 st1, G1 = _cap_partials(abi, stream, st1, new, shift_row=True)
             else:
-                # F1
-                dsc = abi.rowlin_ex(m, d, 3 * d, x=y_prev if li else x_in, w=w_in, bias=b_in, y=qkv, **bn_prev)
-                abi.rowlin_fwd_ex(dsc, stream)
-                if USE_ATTN_OUT and not lowp and abi.attn_out_supported(n, d, heads):
-                    # F2 + F3 in one launch, one workgroup per (graph, 32 query rows) (csrc/attnout.hip)
-                    G1 = abi.attn_out_stat_rows(b, n)
-                    st1 = new(G1 + 1, 2, d)
-                    abi.attn_out_fwd(b, n, scale, stream, tie_qk=tie, x=y_prev if li else x_in, x_bn=prm_prev, w_out=w_o,
-                                     b_out=b_o, pe=pe_c, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
-                                     attn_stats=ast, attn=attn, y=y1, y_stats=st1, y_shift=layer.norm1.running_mean,
-                                     sums=(pending.take_fwd() if (pending is not None and li == 0) else ()))
-                    st1, G1 = _cap_partials(abi, stream, st1, new, shift_row=True)
-                else:
-                    # F2
-                    q, k, v = _views(qkv, n, b, heads, dh)
-                    if tie:
-                        k = q
-                    abi.attn_fwd(q, k, v, pe_c, n_real, out.permute(1, 0, 2, 3), attn, ast, scale, stream)
-                    # F3
-                    G1 = G
-                    st1 = new(G1 + 1, 2, d)
-                    dsc = abi.rowlin_ex(m, d, d, x=out.view(m, d), w=w_o, bias=b_o, rowscale=degree_rows,
-                                        residual=y_prev, res_bn=prm_prev, y=y1, stats=st1,
-                                        stats_shift=layer.norm1.running_mean)
-                    abi.rowlin_fwd_ex(dsc, stream)
+                st1, G1 = _attn_fwd_unfused(g, li, y_prev, w_in, b_in, w_o, b_o, bufs, pending, bn_in=bn_prev, x_bn=prm_prev,
+                                            y_shift=layer.norm1.running_mean)
             h, prm1 = newt(m, ff), new(4, d)
             n1 = layer.norm1
             bn1 = dict(x_stats=st1, Gx=G1, x_gamma=g1, x_beta=be1, x_bn_out=prm1, x_rmean=n1.running_mean,
@@ -393,19 +577,8 @@ class FusedEncoderStackFn(torch.autograd.Function):
                                  final, prm2, last.running_mean, last.running_var, float(last.momentum),
                                  float(last.eps), stream, nbt=last.num_batches_tracked)
         ctx.tail = tail
-        ctx.pending = pending
         saved[-1]['prm2'] = prm2
-        ctx.saved_state = saved
-        if CAPTURE_SAVED is not None:
-            CAPTURE_SAVED.append(saved)
-        ctx.meta = (n, b, d, heads, dh, tie, scale, G, nl)
-        ctx.aux = (pe_c, degree_rows, n_real)
-        ctx.params = params
-        ctx.owner = layers[0] if len(layers) else None
-        if attn is not None:
-            ctx.mark_non_differentiable(attn)
-        concat_last = (out32 if lowp else saved[-1]['out']).view(n, b, d)
-        return final.view(n, b, d), concat_last, attn
+        return _finish_forward(ctx, g, layers, params, saved, final, out32, attn)
 
     @staticmethod
     def backward(ctx, d_final, d_concat_last, _d_attn):
@@ -414,38 +587,15 @@ class FusedEncoderStackFn(torch.autograd.Function):
             # nothing downstream used the stack (e.g. a loss on the filter coefficients alone: they derive from the
             # DETACHED attention matrix, transformer/models.py:282) - autograd still visits the node, with no gradient
             return (None,) * (8 + len(params))
-        n, b, d, heads, dh, tie, scale, G, nl = ctx.meta
-        pe_c, degree_rows, n_real = ctx.aux
-        abi, stream = _lib.backend(saved[0]['qkv'])
-        m = n * b
-        dev = saved[0]['qkv'].device
-        dt = saved[0]['qkv'].dtype      # storage type of the stack's token tensors (forward)
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-        grads = [None] * len(params)
-        ff0 = params[6].shape[0]
-        fused_attn = _fused_attn_bwd(abi, b, n, d, heads, tie, dt)
-        # every weight/bias gradient of the stack goes through the split-K partial buffers and ONE deterministic
-        # reduction at the end (instead of one reduction launch per linear)
-        part_f, part_a, tf, ta, wslot = _partial_buffers(abi, new, m, b, n, d, heads, ff0, nl, fused_attn)
-        coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
-        # dW / db of the coefficient generator's linear, left by the filter stage for this backward's LAST launch
-        lin_dw = _lin_dw_request(ctx, abi, stream, lambda rq: fused_attn and dt == torch.float32 and
-                                 abi.attn_block_bwd_dw_supported(b, n, heads, *rq.shape()))
-        total = tf + ta
-        # ONE flat gradient buffer for the whole stack: [weights and biases (reduced partials) | dgamma,
-        # dbeta of norm1 / norm2 of every layer]; every parameter gradient returned below is a view of it,
-        # so a data-parallel trainer all-reduces it in place (parallel.FlatBufferAllReduce)
-        dwdb_all = new(total + nl * 4 * d)
-        bn_tail = dwdb_all[total:].view(nl, 4, d)
-
-        slots = {}
+        g, fused_attn, coeff_req, lin_dw, dcur = _begin_backward(ctx, d_final, lin_dw_rides=True)
+        abi, stream, new, newt = g.abi, g.stream, g.new, g.newt
+        n, b, d, m, nl, G = g.n, g.b, g.d, g.m, g.nl, g.G
+        degree_rows = g.rowscale
+        # the tail: dgamma, dbeta of norm1 / norm2 of every layer, written by the kernels that finalize the BatchNorm backward
+        sl = _GradSlots(g, params, fused_attn, USE_FFN_BWD and abi.ffn_bwd_supported(d, params[6].shape[0]), tail_rows=4)
+        tf, ta = sl.tf, sl.ta
         early_done = None     # 'a' columns already reduced by the last launch (USE_EARLY_COLSUM)
-        if d_final is None:   # only the per-head output of the last layer was used
-            d_final = torch.zeros(n, b, d, dtype=torch.float32, device=dev)
-        if dt != torch.float32 and d_final.dtype != torch.float32:
-            d_final = d_final.float()      # (the stack's output is fp32: so is its gradient)
-        dcur, dcur_b = d_final.contiguous().view(m, d), None
+        dcur_b = None
         if ctx.tail is not None:
             # (StackTail contract) d_final is the gradient w.r.t. BN2(y2); its partial sums came with it
             gs = ctx.tail.gs
@@ -461,66 +611,49 @@ class FusedEncoderStackFn(torch.autograd.Function):
             s = saved[li]
             (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             ff = w1.shape[0]
-            base = li * PER_LAYER
-            fin2, dg2, db2 = new(2, d), bn_tail[li, 2], bn_tail[li, 3]
-            pp, off = wslot('f', d, ff)
-            slots[base + 8] = (off, d, ff)
-            pp1, off1 = wslot('f', ff, d)
-            slots[base + 6] = (off1, ff, d)
+            fin2 = new(2, d)
+            dg2, db2 = sl.norm_tail(li, 1)
+            pp, pp1 = sl.ffn(li, ff)
             dx1 = newt(m, d)
+            # the gradient load applies the BatchNorm backward of norm2 to dcur
+            load2 = dict(g_y=s['y2'], g_bn=s['prm2'], g_sum=gs, Gs=Gs_cur, g_fin_out=fin2, dgamma=dg2, dbeta=db2)
             if USE_FFN_BWD and abi.ffn_bwd_supported(d, ff):
                 # B1 + B2 in one launch (csrc/ffn_bwd.hip): the hidden gradient never leaves the chip
                 G1s = abi.ffn_bwd_blocks(m)
                 gs1 = new(G1s, 2, d)
-                abi.ffn_bwd(m, ff, stream, coeff=(coeff_req if li == nl - 1 else None), Gs=Gs_cur, partial_ptr=pp,
-                            partial_ld=tf, dy=dcur, dy_b=dcur_b, g_y=s['y2'],
-                            g_bn=s['prm2'], g_sum=gs, g_fin_out=fin2, dgamma=dg2, dbeta=db2, h=s['h'], w2=w2, w1=w1,
-                            x=s['y1'], x_bn=s['prm1'], dx=dx1, sum_out=gs1)
+                abi.ffn_bwd(m, ff, stream, coeff=(coeff_req if li == nl - 1 else None), partial_ptr=pp, partial_ld=tf,
+                            dy=dcur, dy_b=dcur_b, h=s['h'], w2=w2, w1=w1, x=s['y1'], x_bn=s['prm1'], dx=dx1, sum_out=gs1,
+                            **load2)
                 gs1, G1s = _cap_partials(abi, stream, gs1, new)
             else:
                 assert dcur_b is None
-                # B1: linear2 backward, gradient = BN2 backward of dcur
-                dh_ = new(m, ff)
-                dsc = abi.rowlin_ex(m, ff, d, x=s['h'], w=w2, dy=dcur, dx=dh_, partial_ptr=pp, partial_ld=tf,
-                                    g_y=s['y2'], g_bn=s['prm2'], g_sum=gs, Gs=Gs_cur, g_fin_out=fin2, dgamma=dg2,
-                                    dbeta=db2)
-                abi.rowlin_bwd_ex(dsc, None, stream)
-                # B2: linear1 backward (+ residual BN2 backward, + sums for BN1 backward)
+                # B2: + residual BN2 backward, + sums for BN1 backward
                 gs1, G1s = new(G, 2, d), G
-                dsc = abi.rowlin_ex(m, d, ff, x=s['y1'], x_bn=s['prm1'], w=w1, dy=dh_, relu_y=s['h'], dx=dx1,
-                                    partial_ptr=pp1, partial_ld=tf, add_dout=dcur, add_y=s['y2'],
-                                    add_bn=s['prm2'], add_fin=fin2, sum_y=s['y1'], sum_bn=s['prm1'], sum_out=gs1)
-                abi.rowlin_bwd_ex(dsc, None, stream)
-            grads[base + 10], grads[base + 11] = dg2, db2
-            fin1, dg1, db1 = new(2, d), bn_tail[li, 0], bn_tail[li, 1]
-            grads[base + 4], grads[base + 5] = dg1, db1
-            a_done = wslot.cur['a']      # 'a' columns of the layers behind this one: complete
-            ppo, offo = wslot('a', d, d)
-            slots[base + 2] = (offo, d, d)
-            ppi, offi = wslot('a', 3 * d, d)
-            slots[base + 0] = (offi, 3 * d, d)
-            d2 = d_concat_last if (li == nl - 1 and d_concat_last is not None) else None
+                _ffn_bwd_unfused(g, s, s['y1'], w2, w1, dcur, dx1, pp, pp1, tf, load=load2,
+                                 lin1=dict(x_bn=s['prm1'], add_dout=dcur, add_y=s['y2'], add_bn=s['prm2'], add_fin=fin2,
+                                           sum_y=s['y1'], sum_bn=s['prm1'], sum_out=gs1))
+            fin1 = new(2, d)
+            dg1, db1 = sl.norm_tail(li, 0)
+            a_done = sl.cur['a']      # 'a' columns of the layers behind this one: complete
+            ppo, ppi = sl.attn(li)
+            d2 = d_concat_last if li == nl - 1 else None      # (a second gradient into the last layer's per-head outputs)
             if fused_attn:
                 # B3 + B4 + B5 in one launch, one workgroup per graph (csrc/block_bwd.hip): dconcat and dqkv stay on chip
                 dx0 = newt(m, d)
                 early = ()
                 if li == 0 and USE_EARLY_COLSUM and b <= 160:   # (measured: a gain only while this launch leaves CUs idle)
                     # the last launch of this backward: everything but its own partial columns is reduced beside it
-                    early = [(part_f, dwdb_all[:tf])]
-                    if a_done > 0:
-                        early.append((part_a[:, :a_done], dwdb_all[tf:tf + a_done]))
-                    early_done = a_done
+                    early, early_done = sl.early(a_done), a_done
                 # the layer below takes the gradient in two parts iff its FFN backward is the fused kernel
                 split = (USE_ATTN_BLOCK_SPLIT and li > 0 and USE_FFN_BWD and abi.attn_block_bwd_blocks(b) == b
                          and abi.ffn_bwd_supported(d, params[(li - 1) * PER_LAYER + 6].shape[0]))
                 dx0b = newt(m, d) if split else None
                 GB = abi.attn_block_bwd_blocks(b)
                 gs_prev = new(2 * GB, 2, d) if li > 0 else None
-                abi.attn_block_bwd(b, n, scale, stream, heads=heads, Gs=G1s, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'],
-                                   dx_b=dx0b,
-                                   bn1=s['prm1'], g_sum=gs1, fin_out=fin1, dgamma=dg1, dbeta=db1, rowscale=degree_rows,
-                                   w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
-                                   dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
+                abi.attn_block_bwd(b, n, g.scale, stream, heads=g.heads, Gs=G1s, partial_ptr=ppo, partial_ld=ta, dy=dx1,
+                                   y1=s['y1'], dx_b=dx0b, bn1=s['prm1'], g_sum=gs1, fin_out=fin1, dgamma=dg1, dbeta=db1,
+                                   rowscale=degree_rows, w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
+                                   dout2=None if d2 is None else d2.contiguous().view(m, d), pe=g.pe, n_real=g.n_real,
                                    attn_stats=s['ast'], x0=s['x0'], bn0=s['prm0'] if li > 0 else None, dx=dx0,
                                    sum_out=gs_prev, sums=early, lin_dw=(lin_dw if li == 0 else None))
                 Gs_next = 2 * GB
@@ -528,62 +661,24 @@ class FusedEncoderStackFn(torch.autograd.Function):
                     gs_prev, Gs_next = _cap_partials(abi, stream, gs_prev, new)
                 dcur, dcur_b, gs, Gs_cur = dx0, dx0b, gs_prev, Gs_next
                 continue
-            # B3: out_proj backward, gradient = degree * BN1 backward of dx1
-            dconcat = new(m, d)
-            dsc = abi.rowlin_ex(m, d, d, x=s['out'].view(m, d), w=w_o, dy=dx1, rowscale=degree_rows, dx=dconcat,
-                                partial_ptr=ppo, partial_ld=ta, g_y=s['y1'], g_bn=s['prm1'], g_sum=gs1, Gs=G1s,
-                                g_fin_out=fin1, dgamma=dg1, dbeta=db1)
-            abi.rowlin_bwd_ex(dsc, None, stream)
-            dout2 = None
-            if d2 is not None:
-                if abi.attn_bwd_takes_dout2(n, dh, heads=heads):   # added inside the kernel's loads
-                    dout2 = d2.contiguous().view(n, b, heads, dh).permute(1, 0, 2, 3)
-                else:
-                    dconcat = dconcat + d2.contiguous().view(m, d)
-            # B4: attention backward
-            q, k, v = _views(s['qkv'], n, b, heads, dh)
-            if tie:
-                k = q
-            dqkv = new(m, 3 * d)
-            dq, dk, dv = _views(dqkv, n, b, heads, dh)
-            delta = new(b, heads, n)
-            abi.attn_bwd(q, k, v, pe_c, n_real, s['out'].permute(1, 0, 2, 3),
-                         dconcat.view(n, b, heads, dh).permute(1, 0, 2, 3), s['ast'], delta, dq, dk, dv, scale,
-                         stream, dout2=dout2)
-            if tie:
-                dqkv[:, :d] += dqkv[:, d:2 * d]
-                dqkv[:, d:2 * d] = 0
-            # B5: in_proj backward (+ residual BN1 backward, + sums for the previous layer's BN2)
-            dx0 = new(m, d)
+            # B3: gradient = degree * BN1 backward of dx1; B5: + residual BN1 backward, + sums for the previous layer's BN2
             gs_prev = new(G, 2, d) if li > 0 else None
-            dsc = abi.rowlin_ex(m, d, 3 * d, x=s['x0'], x_bn=s['prm0'], w=w_in, dy=dqkv, dx=dx0,
-                                partial_ptr=ppi, partial_ld=ta, add_dout=dx1, add_y=s['y1'],
-                                add_bn=s['prm1'], add_fin=fin1, sum_y=(s['x0'] if li > 0 else None),
-                                sum_bn=s['prm0'], sum_out=gs_prev)
-            abi.rowlin_bwd_ex(dsc, None, stream)
-            Gs_next = G
-            dcur, dcur_b, gs, Gs_cur = dx0, None, gs_prev, Gs_next
+            dx0 = _attn_bwd_unfused(
+                g, s, w_o, w_in, dx1, d2, ppo, ppi, ta,
+                load=dict(g_y=s['y1'], g_bn=s['prm1'], g_sum=gs1, Gs=G1s, g_fin_out=fin1, dgamma=dg1, dbeta=db1),
+                in_proj=dict(x_bn=s['prm0'], add_dout=dx1, add_y=s['y1'], add_bn=s['prm1'], add_fin=fin1,
+                             sum_y=(s['x0'] if li > 0 else None), sum_bn=s['prm0'], sum_out=gs_prev))
+            dcur, dcur_b, gs, Gs_cur = dx0, None, gs_prev, G
         assert dcur_b is None
-        assert wslot.cur == {'f': tf, 'a': ta}
-        # ... and whatever column sums the filter stage left for this launch (functional.PendingSums)
-        if early_done is not None:
-            last = [(part_a[:, early_done:], dwdb_all[tf + early_done:total])]
-        else:
-            last = [(part_f, dwdb_all[:tf]), (part_a, dwdb_all[tf:total])]
-        abi.colsum_multi(last + _take_pending(ctx), stream)
-        if ctx.owner is not None:
-            STACK_FLAT_GRAD[ctx.owner] = dwdb_all
-        for idx, (off, no, ki) in slots.items():
-            grads[idx] = dwdb_all[off:off + no * ki].view(no, ki)
-            if params[idx + 1] is not None:
-                grads[idx + 1] = dwdb_all[off + no * ki:off + no * ki + no]
-        return (dcur.view(n, b, d), None, None, None, None, None, None, None) + tuple(grads)
+        return _finish_backward(ctx, g, sl, dcur, sl.rest(early_done))
 
 
 class FusedLayerNormStackFn(torch.autograd.Function):
     """The LayerNorm variant (batch_norm=False: the default of the reference's TU / molhiv / SBM scripts,
-    experiments/run_transformer_gengcn_cv.py:56).  LayerNorm is row-local, so the normalised activations
-    ARE materialised (feta_layernorm_fwd after each sub-layer) and every kernel reads plain operands.
+    experiments/run_transformer_gengcn_cv.py:56).  Three forward forms: on load (_ln_on_load_forward), on load as one
+    launch (_ln_one_launch_forward) and, where a launch of the stack is not one of the four fused kernels, the
+    MATERIALISED form here: LayerNorm is row-local, so the normalised activations are written (feta_layernorm_fwd after
+    each sub-layer) and every kernel reads plain operands.
     Per layer, forward (4 launches where csrc/block.hip and csrc/ffn.hip take the shape, else 7):
         y1 = x0 + degree * out_proj(attention(in_proj(x0)))     feta_attn_block_fwd
         x1 = LN1(y1)                                             feta_layernorm_fwd
@@ -596,74 +691,29 @@ class FusedLayerNormStackFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, pe, degree_rows, n_real, layers, need_attn, tail, pending, *params):
-        abi, stream = _lib.backend(src, pe, n_real)
-        ctx.set_materialize_grads(False)
         assert tail is None   # (LayerNorm is row-local: its output is materialised by feta_layernorm_fwd)
-        ctx.pending = pending
-        ctx.on_load = (len(layers) > 0 and ln_on_load_supported(abi, layers, src.shape[0], src.shape[1], src.shape[2],
-                                                                 layers[0].self_attn.tie_qk))
+        g, x_in = _begin_forward(ctx, src, pe, degree_rows, n_real, layers, pending)
+        abi, stream, new, newt = g.abi, g.stream, g.new, g.newt
+        n, b, d, m, nl, heads = g.n, g.b, g.d, g.m, g.nl, g.heads
+        ctx.on_load = ln_on_load_supported(abi, layers, n, b, d, g.tie)
         if ctx.on_load:
             one = getattr(layers, 'one_launch', None)
-            if ((USE_LN_ONE_LAUNCH if one is None else one)
-                    and ln_one_launch_supported(abi, layers, src.shape[0], src.shape[1], src.shape[2],
-                                                layers[0].self_attn.tie_qk, src.dtype)):
-                return _ln_one_launch_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params)
-            return _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params)
-        if len(layers):
-            STACK_FLAT_GRAD.pop(layers[0], None)
-        n, b, d = src.shape
-        m = n * b
-        nl = len(layers)
-        heads = layers[0].self_attn.num_heads
-        dh = d // heads
-        tie = layers[0].self_attn.tie_qk
-        scale = float(dh) ** -0.5
-        dev = src.device
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        # bf16 storage: as in the BatchNorm stack - bf16 token tensors inside, fp32 out of the last layer
-        dt = src.dtype
-        lowp = dt != torch.float32
-        newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-        x_in = src.contiguous().view(m, d)
-        pe_c = None if pe is None else pe.contiguous()
+            if (USE_LN_ONE_LAUNCH if one is None else one) and ln_one_launch_supported(abi, layers, n, b, d, g.tie, g.dt):
+                return _ln_one_launch_forward(ctx, g, x_in, layers, need_attn, pending, params)
+            return _ln_on_load_forward(ctx, g, x_in, layers, need_attn, pending, params)
         block = USE_ATTN_BLOCK and abi.attn_block_supported(n, d, heads)
-        if lowp and not lowp_stack_supported(abi, layers, n, b, d):
-            raise NotImplementedError('bf16 storage: the fused stack needs d_model = 64, 4 heads, N <= 64')
         saved = []
-        attn = None
-        out32 = None
         for li, layer in enumerate(layers):
             (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             ff = w1.shape[0]
-            want = need_attn and li == nl - 1
-            attn = new(b, heads, n, n) if want else None
-            ast = new(b, heads, n, 2)
-            qkv = newt(m, 3 * d)
-            out = torch.empty((n, b, heads, dh), dtype=dt, device=dev)
-            if lowp and li == nl - 1:
-                out32 = new(n, b, heads, dh)
-            y1 = newt(m, d)
+            bufs = attn, ast, qkv, out, out32, y1 = _attn_alloc(g, li, need_attn)
             if block:
-                abi.attn_block_fwd(b, n, scale, stream, heads=heads, tie_qk=tie, x=x_in, w_in=w_in, b_in=b_in, w_out=w_o,
-                                   b_out=b_o, pe=pe_c, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
+                abi.attn_block_fwd(b, n, g.scale, stream, heads=heads, tie_qk=g.tie, x=x_in, w_in=w_in, b_in=b_in, w_out=w_o,
+                                   b_out=b_o, pe=g.pe, n_real=n_real, rowscale=degree_rows, qkv=qkv, out=out,
                                    attn_stats=ast, attn=attn, y=y1, y_stats=new(abi.attn_block_stat_rows(b, n) + 1, 2, d),   # (statistics unused)
-                                   out_f32=(out32 if li == nl - 1 else None),
-                                   sums=(pending.take_fwd() if (pending is not None and li == 0) else ()))
+                                   out_f32=out32, sums=_fwd_sums(pending, li))
             else:
-                dsc = abi.rowlin_ex(m, d, 3 * d, x=x_in, w=w_in, bias=b_in, y=qkv)
-                abi.rowlin_fwd_ex(dsc, stream)
-                if USE_ATTN_OUT and not lowp and abi.attn_out_supported(n, d, heads):
-                    abi.attn_out_fwd(b, n, scale, stream, tie_qk=tie, x=x_in, w_out=w_o, b_out=b_o, pe=pe_c, n_real=n_real,
-                                     rowscale=degree_rows, qkv=qkv, out=out, attn_stats=ast, attn=attn, y=y1,
-                                     sums=(pending.take_fwd() if (pending is not None and li == 0) else ()))
-                else:
-                    q, k, v = _views(qkv, n, b, heads, dh)
-                    if tie:
-                        k = q
-                    abi.attn_fwd(q, k, v, pe_c, n_real, out.permute(1, 0, 2, 3), attn, ast, scale, stream)
-                    dsc = abi.rowlin_ex(m, d, d, x=out.view(m, d), w=w_o, bias=b_o, rowscale=degree_rows,
-                                        residual=x_in, y=y1)
-                    abi.rowlin_fwd_ex(dsc, stream)
+                _attn_fwd_unfused(g, li, x_in, w_in, b_in, w_o, b_o, bufs, pending)
             h, y2 = newt(m, ff), newt(m, d)
             # norm1 on load (ABI 9) where the feed-forward half runs as its two fused kernels: x1 is never written, the
             # backward recomputes it from y1 and takes the LayerNorm backward of norm2 on its gradient load
@@ -699,19 +749,8 @@ class FusedLayerNormStackFn(torch.autograd.Function):
             saved.append(dict(x0=x_in, qkv=qkv, out=out, ast=ast, y1=y1, lst1=lst1, x1=x1, h=h, y2=y2, lst2=lst2,
                               ffn_on_load=ffn_on_load))
             x_in = x2
-        ctx.saved_state = saved
-        if CAPTURE_SAVED is not None:
-            CAPTURE_SAVED.append(saved)
-        ctx.eps = [(float(l.norm1.eps), float(l.norm2.eps)) for l in layers]
-        ctx.meta = (n, b, d, heads, dh, tie, scale, nl)
-        ctx.aux = (pe_c, degree_rows, n_real)
-        ctx.params = params
-        ctx.owner = layers[0] if len(layers) else None
-        if attn is not None:
-            ctx.mark_non_differentiable(attn)
-        concat_last = (out32 if lowp else saved[-1]['out']).view(n, b, d)
         # (a fresh tensor object for the output: the saved x2 of the last layer is not handed out)
-        return x_in.view(n, b, d), concat_last, attn
+        return _finish_forward(ctx, g, layers, params, saved, x_in, out32, attn)
 
     @staticmethod
     def backward(ctx, d_final, d_concat_last, _d_attn):
@@ -720,62 +759,38 @@ class FusedLayerNormStackFn(torch.autograd.Function):
             return (None,) * (8 + len(params))      # (see FusedEncoderStackFn.backward)
         if ctx.on_load:
             return _ln_on_load_backward(ctx, d_final, d_concat_last)
-        n, b, d, heads, dh, tie, scale, nl = ctx.meta
-        pe_c, degree_rows, n_real = ctx.aux
-        abi, stream = _lib.backend(saved[0]['qkv'])
-        m = n * b
-        dev = saved[0]['qkv'].device
-        dt = saved[0]['qkv'].dtype
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
+        g, fused_attn, coeff_req, _, dcur = _begin_backward(ctx, d_final)
+        abi, stream, new, newt = g.abi, g.stream, g.new, g.newt
+        n, b, d, m, nl = g.n, g.b, g.d, g.m, g.nl
         GL = abi.layernorm_blocks(m)
-        grads = [None] * len(params)
-        ff0 = params[6].shape[0]
-        fused_attn = _fused_attn_bwd(abi, b, n, d, heads, tie, dt)
         # feed-forward half on its fused kernels with the LayerNorms on load (ABI 9): norm2's backward is taken on the
         # gradient load of feta_ffn_bwd ([dgamma2 | dbeta2] in its partial rows, behind db1), x1 = LN1(y1) on its operand
         # load; norm1's backward stays a launch (no saved statistics: recomputed from y1)
         ffn_on_load = all(s_['ffn_on_load'] for s_ in saved)     # (one feed-forward width per stack: all or none)
-        part_f, part_a, tf, ta, wslot = _partial_buffers(
-            abi, new, m, b, n, d, heads, ff0, nl, fused_attn, ln_f=ffn_on_load,
-            ffn_fused=bool(ffn_on_load or (USE_FFN_BWD and abi.ffn_bwd_supported(d, ff0))))
-        coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
-        _lin_dw_request(ctx, abi, stream, None)      # (no launch of this backward carries it: the library, here)
-        total = tf + ta
         lnw = 2 if ffn_on_load else 4               # LayerNorm partial columns per layer that come from feta_layernorm_bwd
+        # the tail: dgamma1, dbeta1 (, dgamma2, dbeta2) per layer
+        sl = _GradSlots(g, params, fused_attn, bool(ffn_on_load or (USE_FFN_BWD and abi.ffn_bwd_supported(d, params[6].shape[0]))),
+                        ln_f=ffn_on_load, tail_rows=lnw)
+        tf, ta = sl.tf, sl.ta
         ln_part = new(GL, nl * lnw * d)
-        dwdb_all = new(total + nl * lnw * d)        # [feed-forward slots | attention slots | LayerNorm tail]
-        ln_tail = dwdb_all[total:].view(nl, lnw, d)   # dgamma1, dbeta1 (, dgamma2, dbeta2) per layer
 
         def ln_bwd(dout, y, stats, gamma, li, which, eps=1e-5):
             dy = newt(m, d)
             abi.layernorm_bwd(dout, y, stats, gamma, dy, None, None, stream, partial_ld=nl * lnw * d,
                               partial_ptr=ln_part.data_ptr() + 4 * (li * lnw + 2 * which) * d, eps=eps)
+            sl.norm_tail(li, which)
             return dy
 
-        slots = {}
-        if d_final is None:
-            d_final = torch.zeros(n, b, d, dtype=torch.float32, device=dev)
-        if dt != torch.float32 and d_final.dtype != torch.float32:
-            d_final = d_final.float()
-        dcur = d_final.contiguous().view(m, d)
         for li in range(nl - 1, -1, -1):
             s = saved[li]
             (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             ff = w1.shape[0]
-            base = li * PER_LAYER
             eps1, eps2 = ctx.eps[li]
             if not ffn_on_load:
                 dy2 = ln_bwd(dcur, s['y2'], s['lst2'], g2, li, 1, eps2)
-                grads[base + 10], grads[base + 11] = ln_tail[li, 2], ln_tail[li, 3]
-            pp, off = wslot('f', d, ff)
-            slots[base + 8] = (off, d, ff)
-            pp1, off1 = wslot('f', ff, d)
-            slots[base + 6] = (off1, ff, d)
+            pp, pp1 = sl.ffn(li, ff, ln=ffn_on_load)
             dx1 = newt(m, d)
             if ffn_on_load:
-                offl = wslot.raw('f', 2 * d)
-                grads[base + 10], grads[base + 11] = dwdb_all[offl:offl + d], dwdb_all[offl + d:offl + 2 * d]
                 abi.ffn_bwd(m, ff, stream, coeff=(coeff_req if li == nl - 1 else None), partial_ptr=pp, partial_ld=tf,
                             dy=dcur, g_y=s['y2'], g_ln_gamma=g2, ln_eps=eps2, h=s['h'], w2=w2, w1=w1, x=s['y1'],
                             x_ln_gamma=g1, x_ln_beta=be1, dx=dx1)
@@ -785,70 +800,23 @@ class FusedLayerNormStackFn(torch.autograd.Function):
                             dy=dy2, h=s['h'], w2=w2, w1=w1, x=s['x1'],
                             dx=dx1)
             else:
-                # linear2, then linear1 with the residual gradient dy2 added in its dX epilogue
-                dh_ = new(m, ff)
-                dsc = abi.rowlin_ex(m, ff, d, x=s['h'], w=w2, dy=dy2, dx=dh_, partial_ptr=pp, partial_ld=tf)
-                abi.rowlin_bwd_ex(dsc, None, stream)
-                dsc = abi.rowlin_ex(m, d, ff, x=s['x1'], w=w1, dy=dh_, relu_y=s['h'], dx=dx1, partial_ptr=pp1,
-                                    partial_ld=tf, add_plain=dy2)
-                abi.rowlin_bwd_ex(dsc, None, stream)
+                _ffn_bwd_unfused(g, s, s['x1'], w2, w1, dy2, dx1, pp, pp1, tf, lin1=dict(add_plain=dy2))
             dy1 = ln_bwd(dx1, s['y1'], s['lst1'], g1, li, 0, eps1)     # (lst1 None: LayerNorm on load - recomputed)
-            grads[base + 4], grads[base + 5] = ln_tail[li, 0], ln_tail[li, 1]
-            ppo, offo = wslot('a', d, d)
-            slots[base + 2] = (offo, d, d)
-            ppi, offi = wslot('a', 3 * d, d)
-            slots[base + 0] = (offi, 3 * d, d)
-            d2 = d_concat_last if (li == nl - 1 and d_concat_last is not None) else None
+            ppo, ppi = sl.attn(li)
+            d2 = d_concat_last if li == nl - 1 else None      # (a second gradient into the last layer's per-head outputs)
             if fused_attn:
                 # out_proj + attention + in_proj backward in one launch, one workgroup per graph (csrc/block_bwd.hip)
-                dx0 = newt(m, d)
-                abi.attn_block_bwd(b, n, scale, stream, heads=heads, partial_ptr=ppo, partial_ld=ta, dy=dy1, rowscale=degree_rows,
-                                   w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
-                                   dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
-                                   attn_stats=s['ast'], x0=s['x0'], dx=dx0)
-                dcur = dx0
-                continue
-            # out_proj (gradient scaled by degree), attention, in_proj with the residual gradient dy1
-            dconcat = new(m, d)
-            dsc = abi.rowlin_ex(m, d, d, x=s['out'].view(m, d), w=w_o, dy=dy1, rowscale=degree_rows, dx=dconcat,
-                                partial_ptr=ppo, partial_ld=ta)
-            abi.rowlin_bwd_ex(dsc, None, stream)
-            dout2 = None
-            if d2 is not None:
-                if abi.attn_bwd_takes_dout2(n, dh, heads=heads):
-                    dout2 = d2.contiguous().view(n, b, heads, dh).permute(1, 0, 2, 3)
-                else:
-                    dconcat = dconcat + d2.contiguous().view(m, d)
-            q, k, v = _views(s['qkv'], n, b, heads, dh)
-            if tie:
-                k = q
-            dqkv = new(m, 3 * d)
-            dq, dk, dv = _views(dqkv, n, b, heads, dh)
-            delta = new(b, heads, n)
-            abi.attn_bwd(q, k, v, pe_c, n_real, s['out'].permute(1, 0, 2, 3),
-                         dconcat.view(n, b, heads, dh).permute(1, 0, 2, 3), s['ast'], delta, dq, dk, dv, scale,
-                         stream, dout2=dout2)
-            if tie:
-                dqkv[:, :d] += dqkv[:, d:2 * d]
-                dqkv[:, d:2 * d] = 0
-            dx0 = new(m, d)
-            dsc = abi.rowlin_ex(m, d, 3 * d, x=s['x0'], w=w_in, dy=dqkv, dx=dx0, partial_ptr=ppi, partial_ld=ta,
-                                add_plain=dy1)
-            abi.rowlin_bwd_ex(dsc, None, stream)
-            dcur = dx0
-        assert wslot.cur == {'f': tf, 'a': ta}
-        abi.colsum_multi([(part_f, dwdb_all[:tf]), (part_a, dwdb_all[tf:total]), (ln_part, dwdb_all[total:])]
-                         + _take_pending(ctx), stream)
-        if ctx.owner is not None:
-            STACK_FLAT_GRAD[ctx.owner] = dwdb_all
-        for idx, (off, no, ki) in slots.items():
-            grads[idx] = dwdb_all[off:off + no * ki].view(no, ki)
-            if params[idx + 1] is not None:
-                grads[idx + 1] = dwdb_all[off + no * ki:off + no * ki + no]
-        return (dcur.view(n, b, d), None, None, None, None, None, None, None) + tuple(grads)
+                dcur = newt(m, d)
+                abi.attn_block_bwd(b, n, g.scale, stream, heads=g.heads, partial_ptr=ppo, partial_ld=ta, dy=dy1,
+                                   rowscale=g.rowscale, w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
+                                   dout2=None if d2 is None else d2.contiguous().view(m, d), pe=g.pe, n_real=g.n_real,
+                                   attn_stats=s['ast'], x0=s['x0'], dx=dcur)
+            else:
+                dcur = _attn_bwd_unfused(g, s, w_o, w_in, dy1, d2, ppo, ppi, ta, in_proj=dict(add_plain=dy1))
+        return _finish_backward(ctx, g, sl, dcur, sl.rest() + [(ln_part, sl.flat[sl.total:])])
 
 
-def _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params):
+def _ln_on_load_forward(ctx, g, x_pre, layers, need_attn, pending, params):
     """LayerNorm stack with the LayerNorm applied by the consumer of each pre-norm tensor (ABI 9).  Per layer, forward
     (2 launches):
         y1 = x0 + degree * out_proj(attention(in_proj(x0))),  x0 = LN2_prev(y2_prev) on load     feta_attn_block_fwd
@@ -856,41 +824,19 @@ def _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, 
     and ONE feta_layernorm_fwd at the end of the stack (norm2 of the last layer: the output is handed out).  Backward
     (2 launches per layer + one reduction): feta_ffn_bwd takes the gradient w.r.t. LN2(y2) and applies the LayerNorm
     backward where it loads the gradient rows, feta_attn_block_bwd the same for LN1; [dgamma | dbeta] ride in the
-    kernels' split-K partial rows.  No normalised activation is written between the kernels."""
-    if len(layers):
-        STACK_FLAT_GRAD.pop(layers[0], None)
-    n, b, d = src.shape
-    m = n * b
-    nl = len(layers)
-    heads = layers[0].self_attn.num_heads
-    dh = d // heads
-    scale = float(dh) ** -0.5
-    dev = src.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    dt = src.dtype
-    lowp = dt != torch.float32
-    newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-    if lowp and not lowp_stack_supported(abi, layers, n, b, d):
-        raise NotImplementedError('bf16 storage: the fused stack needs d_model = 64, 4 heads, N <= 64')
-    x_pre = src.contiguous().view(m, d)      # pre-norm input rows of the layer (layer 0: the stack input itself)
-    pe_c = None if pe is None else pe.contiguous()
+    kernels' split-K partial rows.  No normalised activation is written between the kernels.
+    x_pre: the pre-norm input rows of the layer (layer 0: the stack input itself)."""
+    abi, stream, new, newt = g.abi, g.stream, g.new, g.newt
+    n, b, d, m, nl = g.n, g.b, g.d, g.m, g.nl
     saved = []
-    attn = out32 = None
     ln_prev = {}
     for li, layer in enumerate(layers):
         (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
         ff = w1.shape[0]
-        attn = new(b, heads, n, n) if (need_attn and li == nl - 1) else None
-        ast = new(b, heads, n, 2)
-        qkv = newt(m, 3 * d)
-        out = torch.empty((n, b, heads, dh), dtype=dt, device=dev)
-        if lowp and li == nl - 1:
-            out32 = new(n, b, heads, dh)
-        y1 = newt(m, d)
-        abi.attn_block_fwd(b, n, scale, stream, heads=heads, x=x_pre, w_in=w_in, b_in=b_in, w_out=w_o, b_out=b_o, pe=pe_c, n_real=n_real,
-                           rowscale=degree_rows, qkv=qkv, out=out, attn_stats=ast, attn=attn, y=y1, y_stats=None,
-                           out_f32=(out32 if li == nl - 1 else None),
-                           sums=(pending.take_fwd() if (pending is not None and li == 0) else ()), **ln_prev)
+        attn, ast, qkv, out, out32, y1 = _attn_alloc(g, li, need_attn)
+        abi.attn_block_fwd(b, n, g.scale, stream, heads=g.heads, x=x_pre, w_in=w_in, b_in=b_in, w_out=w_o, b_out=b_o, pe=g.pe,
+                           n_real=g.n_real, rowscale=g.rowscale, qkv=qkv, out=out, attn_stats=ast, attn=attn, y=y1,
+                           y_stats=None, out_f32=out32, sums=_fwd_sums(pending, li), **ln_prev)
         h = newt(m, ff)
         y2 = new(m, d) if li == nl - 1 else newt(m, d)    # (what leaves the stack is fp32 whatever the storage type)
         # norm2 of the LAST layer is what the stack hands out: the feed-forward kernel writes it beside y2 from its epilogue
@@ -900,137 +846,89 @@ def _ln_on_load_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, 
             final = new(m, d)
             ln_out = dict(y_ln_out=final, y_ln_gamma=g2, y_ln_beta=be2, y_ln_eps=float(layer.norm2.eps))
         abi.ffn_fwd(m, ff, stream, eps=float(layer.norm1.eps), x=y1, x_ln_gamma=g1, x_ln_beta=be1, w1=w1, b1=bb1, w2=w2,
-                    b2=bb2, h=h, y=y2, y_stats=None, coeff=_coeff_fwd_role(pending, li, nl, attn, n_real), **ln_out)
+                    b2=bb2, h=h, y=y2, y_stats=None, coeff=_coeff_fwd_role(pending, li, nl, attn, g.n_real), **ln_out)
         saved.append(dict(x0=x_pre, qkv=qkv, out=out, ast=ast, y1=y1, h=h, y2=y2))
         x_pre = y2
         ln_prev = dict(x_ln_gamma=g2, x_ln_beta=be2, eps=float(layer.norm2.eps))
     if not USE_LN_EPILOGUE:
         # norm2 of the last layer as a launch of its own (FETA_LN_EPILOGUE=0: A/B timing)
-        last = layers[-1].norm2
         final = new(m, d)
-        abi.layernorm_fwd(x_pre, params[(nl - 1) * PER_LAYER + 10], params[(nl - 1) * PER_LAYER + 11], float(last.eps), final,
-                          new(m, 2), stream)
-    ctx.saved_state = saved
-    if CAPTURE_SAVED is not None:
-        CAPTURE_SAVED.append(saved)
-    ctx.meta = (n, b, d, heads, dh, False, scale, nl)
-    ctx.aux = (pe_c, degree_rows, n_real)
-    ctx.params = params
-    ctx.eps = [(float(l.norm1.eps), float(l.norm2.eps)) for l in layers]
-    ctx.owner = layers[0] if len(layers) else None
-    if attn is not None:
-        ctx.mark_non_differentiable(attn)
-    concat_last = (out32 if lowp else saved[-1]['out']).view(n, b, d)
-    return final.view(n, b, d), concat_last, attn
+        abi.layernorm_fwd(x_pre, g2, be2, float(layers[-1].norm2.eps), final, new(m, 2), stream)
+    return _finish_forward(ctx, g, layers, params, saved, final, out32, attn)
 
 
-def _ln_one_launch_forward(ctx, abi, stream, src, pe, degree_rows, n_real, layers, need_attn, pending, params):
+def _encoder_table(layers, params, contiguous=False, running_stats=False):
+    """The feta_encoder_layer table of a one-launch stack (feta_encoder_fwd_save, feta_encoder_infer[_ex]) as _abi takes
+    it: one dict per layer out of the flat parameter list.  contiguous: copy what is not (the caller holds no autograd
+    node that would keep the strides); running_stats: BatchNorm in eval mode - mean and variance of norm1 / norm2."""
+    if contiguous:
+        t = lambda p: None if p is None else p.detach().contiguous()
+    else:
+        t = lambda p: None if p is None else p.detach()
+    table = []
+    for li, l in enumerate(layers):
+        (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
+        e = dict(w_in=t(w_in), b_in=t(b_in), w_out=t(w_o), b_out=t(b_o), n1_gamma=t(g1), n1_beta=t(be1),
+                 w1=t(w1), b1=t(bb1), w2=t(w2), b2=t(bb2), n2_gamma=t(g2), n2_beta=t(be2),
+                 n1_eps=float(l.norm1.eps), n2_eps=float(l.norm2.eps), tie_qk=int(l.self_attn.tie_qk))
+        if running_stats:
+            e.update(n1_mean=t(l.norm1.running_mean), n1_var=t(l.norm1.running_var),
+                     n2_mean=t(l.norm2.running_mean), n2_var=t(l.norm2.running_var))
+        table.append(e)
+    return table
+
+
+def _ln_one_launch_forward(ctx, g, x_pre, layers, need_attn, pending, params):
     """_ln_on_load_forward as ONE launch (feta_encoder_fwd_save): every layer of a graph runs in one workgroup with the
     activations in LDS, and each layer writes what _ln_on_load_backward reads - qkv, out, the softmax statistics, y1, h,
     y2 - in the layouts and storage type of feta_attn_block_fwd / feta_ffn_fwd.  The saved tensors are views of one
     [L, ...] allocation per kind; x0 of layer l > 0 is y2 of layer l - 1.  The pending forward column sums ride in trailing
     workgroups of the launch; the coefficient generator's forward does not (it reads the attention matrix this launch
     writes): pending.coeff_fwd_req stays and FilterCoefficientsFn.forward runs its own launch."""
-    if len(layers):
-        STACK_FLAT_GRAD.pop(layers[0], None)
-    n, b, d = src.shape
-    m = n * b
-    nl = len(layers)
-    heads = layers[0].self_attn.num_heads
-    dh = d // heads
-    scale = float(dh) ** -0.5
-    dev = src.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    dt = src.dtype
-    lowp = dt != torch.float32
-    newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-    if lowp and (pe is not None and pe.dtype != dt):
-        raise TypeError('bf16 stack: pe must be %s as well' % dt)
+    new, newt = g.new, g.newt
+    n, b, d, m, nl, heads, dh, lowp = g.n, g.b, g.d, g.m, g.nl, g.heads, g.dh, g.lowp
     ff = params[6].shape[0]
-    x_pre = src.contiguous().view(m, d)      # layer 0's x0: the tensor the backward reads
-    pe_c = None if pe is None else pe.contiguous()
     attn = new(b, heads, n, n) if need_attn else None
     qkv, out, ast = newt(nl, m, 3 * d), newt(nl, n, b, heads, dh), new(nl, b, heads, n, 2)
     y1, h, y2 = newt(nl, m, d), newt(nl, m, ff), newt(nl, m, d)
     y2_last = new(m, d) if lowp else y2[nl - 1]      # (what leaves the stack is fp32 whatever the storage type)
     out32 = new(n, b, heads, dh) if lowp else None
     final = new(m, d)
-    table = []
-    for li, layer in enumerate(layers):
-        (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
-        t = lambda p: None if p is None else p.detach()
-        table.append(dict(w_in=t(w_in), b_in=t(b_in), w_out=t(w_o), b_out=t(b_o), n1_gamma=t(g1), n1_beta=t(be1),
-                          w1=t(w1), b1=t(bb1), w2=t(w2), b2=t(bb2), n2_gamma=t(g2), n2_beta=t(be2),
-                          n1_eps=float(layer.norm1.eps), n2_eps=float(layer.norm2.eps), tie_qk=0))
-    abi.encoder_fwd_save(b, n, heads, ff, table, stream, dtype=dt, x=x_pre, pe=pe_c, n_real=n_real, rowscale=degree_rows,
-                         y=final, out=out32, attn=attn, qkv=qkv, out_save=out, attn_stats=ast, y1=y1, h=h, y2=y2,
-                         y2_last_f32=(y2_last if lowp else None),
-                         sums=(pending.take_fwd() if pending is not None else ()))
+    g.abi.encoder_fwd_save(b, n, heads, ff, _encoder_table(layers, params), g.stream, dtype=g.dt, x=x_pre, pe=g.pe,
+                           n_real=g.n_real, rowscale=g.rowscale, y=final, out=out32, attn=attn, qkv=qkv, out_save=out,
+                           attn_stats=ast, y1=y1, h=h, y2=y2, y2_last_f32=(y2_last if lowp else None),
+                           sums=(pending.take_fwd() if pending is not None else ()))
     saved = []
     for li in range(nl):
         saved.append(dict(x0=x_pre, qkv=qkv[li], out=out[li], ast=ast[li], y1=y1[li], h=h[li],
                           y2=(y2_last if li == nl - 1 else y2[li])))
         x_pre = saved[-1]['y2']
-    ctx.saved_state = saved
-    if CAPTURE_SAVED is not None:
-        CAPTURE_SAVED.append(saved)
-    ctx.meta = (n, b, d, heads, dh, False, scale, nl)
-    ctx.aux = (pe_c, degree_rows, n_real)
-    ctx.params = params
-    ctx.eps = [(float(l.norm1.eps), float(l.norm2.eps)) for l in layers]
-    ctx.owner = layers[0] if len(layers) else None
-    if attn is not None:
-        ctx.mark_non_differentiable(attn)
-    concat_last = (out32 if lowp else saved[-1]['out']).view(n, b, d)
-    return final.view(n, b, d), concat_last, attn
+    return _finish_forward(ctx, g, layers, params, saved, final, out32, attn)
 
 
 def _ln_on_load_backward(ctx, d_final, d_concat_last):
     saved, params = ctx.saved_state, ctx.params
-    n, b, d, heads, dh, tie, scale, nl = ctx.meta
-    pe_c, degree_rows, n_real = ctx.aux
-    abi, stream = _lib.backend(saved[0]['qkv'])
-    m = n * b
-    dev = saved[0]['qkv'].device
-    dt = saved[0]['qkv'].dtype
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    newt = lambda *s: torch.empty(s, dtype=dt, device=dev)
-    grads = [None] * len(params)
-    ff0 = params[6].shape[0]
-    part_f, part_a, tf, ta, wslot = _partial_buffers(abi, new, m, b, n, d, heads, ff0, nl, True, ln_cols=True, ffn_fused=True)
-    coeff_req = _coeff_bwd_request(ctx, abi, stream, d, params[(nl - 1) * PER_LAYER + 6].shape[0])
-    _lin_dw_request(ctx, abi, stream, None)      # (no launch of this backward carries it: the library, here)
-    total = tf + ta
-    dwdb_all = new(total)      # [feed-forward slots | attention slots], each followed by its LayerNorm's [dgamma | dbeta]
-    slots, ln_slots = {}, {}
-    if d_final is None:
-        d_final = torch.zeros(n, b, d, dtype=torch.float32, device=dev)
-    if d_final.dtype != torch.float32:
-        d_final = d_final.float()      # (the stack's output is fp32: so is its gradient)
-    dcur, dcur_b = d_final.contiguous().view(m, d), None      # gradient w.r.t. LN2(y2) of the layer at hand
+    g, _, coeff_req, _, dcur = _begin_backward(ctx, d_final, fused_attn=True)
+    abi, stream, newt = g.abi, g.stream, g.newt
+    n, b, d, m, nl = g.n, g.b, g.d, g.m, g.nl
+    # no tail: each slot is followed by its LayerNorm's [dgamma | dbeta]
+    sl = _GradSlots(g, params, True, True, ln_f=True, ln_a=True)
+    tf, ta = sl.tf, sl.ta
+    dcur_b = None      # (dcur, dcur_b: gradient w.r.t. LN2(y2) of the layer at hand, in one or two parts)
     GB = abi.attn_block_bwd_blocks(b)
     for li in range(nl - 1, -1, -1):
         s = saved[li]
         (w_in, b_in, w_o, b_o, g1, be1, w1, bb1, w2, bb2, g2, be2) = params[li * PER_LAYER:(li + 1) * PER_LAYER]
         ff = w1.shape[0]
-        base = li * PER_LAYER
         eps1, eps2 = ctx.eps[li]
-        pp, off = wslot('f', d, ff)
-        slots[base + 8] = (off, d, ff)
-        _, off1 = wslot('f', ff, d)
-        slots[base + 6] = (off1, ff, d)
-        ln_slots[base + 10] = wslot.raw('f', 2 * d)
+        pp, _ = sl.ffn(li, ff, ln=True)
         dx1 = newt(m, d)
         # linear2 + linear1 backward; LN2 backward on the gradient load, x1 = LN1(y1) on the operand load
         abi.ffn_bwd(m, ff, stream, coeff=(coeff_req if li == nl - 1 else None), partial_ptr=pp, partial_ld=tf,
                     dy=dcur, dy_b=dcur_b, g_y=s['y2'], g_ln_gamma=g2, ln_eps=eps2, h=s['h'], w2=w2, w1=w1, x=s['y1'],
                     x_ln_gamma=g1, x_ln_beta=be1, dx=dx1)
-        ppo, offo = wslot('a', d, d)
-        slots[base + 2] = (offo, d, d)
-        _, offi = wslot('a', 3 * d, d)
-        slots[base + 0] = (offi, 3 * d, d)
-        ln_slots[base + 4] = wslot.raw('a', 2 * d)
-        d2 = d_concat_last if (li == nl - 1 and d_concat_last is not None) else None
+        ppo, _ = sl.attn(li, ln=True)
+        d2 = d_concat_last if li == nl - 1 else None      # (a second gradient into the last layer's per-head outputs)
         # out_proj + attention + in_proj backward; LN1 backward on the gradient load, x0 = LN2_prev(y2_prev) on load.  The
         # layer below takes its gradient in two parts (two workgroups per graph, one per pair of heads)
         split = USE_ATTN_BLOCK_SPLIT and li > 0 and GB == b
@@ -1039,23 +937,13 @@ def _ln_on_load_backward(ctx, d_final, d_concat_last):
         ln0 = {}
         if li > 0:
             ln0 = dict(x0_ln_gamma=params[(li - 1) * PER_LAYER + 10], x0_ln_beta=params[(li - 1) * PER_LAYER + 11])
-        abi.attn_block_bwd(b, n, scale, stream, heads=heads, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'], ln1_gamma=g1,
-                           ln_eps=eps1, dx_b=dx0b, rowscale=degree_rows, w_out=w_o, w_in=w_in, qkv=s['qkv'], out=s['out'],
-                           dout2=None if d2 is None else d2.contiguous().view(m, d), pe=pe_c, n_real=n_real,
+        abi.attn_block_bwd(b, n, g.scale, stream, heads=g.heads, partial_ptr=ppo, partial_ld=ta, dy=dx1, y1=s['y1'],
+                           ln1_gamma=g1, ln_eps=eps1, dx_b=dx0b, rowscale=g.rowscale, w_out=w_o, w_in=w_in, qkv=s['qkv'],
+                           out=s['out'], dout2=None if d2 is None else d2.contiguous().view(m, d), pe=g.pe, n_real=g.n_real,
                            attn_stats=s['ast'], x0=s['x0'], dx=dx0, **ln0)
         dcur, dcur_b = dx0, dx0b
     assert dcur_b is None
-    assert wslot.cur == {'f': tf, 'a': ta}
-    abi.colsum_multi([(part_f, dwdb_all[:tf]), (part_a, dwdb_all[tf:total])] + _take_pending(ctx), stream)
-    if ctx.owner is not None:
-        STACK_FLAT_GRAD[ctx.owner] = dwdb_all
-    for idx, (off, no, ki) in slots.items():
-        grads[idx] = dwdb_all[off:off + no * ki].view(no, ki)
-        if params[idx + 1] is not None:
-            grads[idx + 1] = dwdb_all[off + no * ki:off + no * ki + no]
-    for idx, off in ln_slots.items():
-        grads[idx], grads[idx + 1] = dwdb_all[off:off + d], dwdb_all[off + d:off + 2 * d]
-    return (dcur.view(n, b, d), None, None, None, None, None, None, None) + tuple(grads)
+    return _finish_backward(ctx, g, sl, dcur, sl.rest())
 
 
 def _coeff_fwd_role(pending, li, nl, attn, n_real):
@@ -1173,17 +1061,10 @@ def encoder_stack_infer(src, pe, degree_rows, n_real, layers, need_attn=True):
     concat = torch.empty_like(y)
     attn = torch.empty(b, heads, n, n, dtype=torch.float32, device=x.device) if need_attn else None
     t = lambda p: None if p is None else p.detach().contiguous()
-    table = []
+    params = []
     for l in layers:
-        a = l.self_attn
-        table.append(dict(
-            w_in=t(a.in_proj_weight), b_in=t(a.in_proj_bias), w_out=t(a.out_proj.weight), b_out=t(a.out_proj.bias),
-            n1_gamma=t(l.norm1.weight), n1_beta=t(l.norm1.bias),
-            n1_mean=t(l.norm1.running_mean) if bn else None, n1_var=t(l.norm1.running_var) if bn else None,
-            w1=t(l.linear1.weight), b1=t(l.linear1.bias), w2=t(l.linear2.weight), b2=t(l.linear2.bias),
-            n2_gamma=t(l.norm2.weight), n2_beta=t(l.norm2.bias),
-            n2_mean=t(l.norm2.running_mean) if bn else None, n2_var=t(l.norm2.running_var) if bn else None,
-            n1_eps=l.norm1.eps, n2_eps=l.norm2.eps, tie_qk=int(a.tie_qk)))
+        params += layer_params(l)
+    table = _encoder_table(layers, params, contiguous=True, running_stats=bn)
     ptrs = dict(x=x, pe=t(pe), n_real=n_real.contiguous(), rowscale=t(degree_rows), y=y, out=concat, attn=attn)
     if l0.storage_dtype == torch.float32:
         abi.encoder_infer(b, n, heads, ff, table, not bn, stream, **ptrs)
