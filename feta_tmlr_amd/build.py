@@ -37,6 +37,9 @@ def build(force=False, report=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     flags = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
              '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC]
+    # extra compiler flags for A/B builds, e.g. FETA_HIPCC_FLAGS="-DFETA_ST_PARTIAL=0" (csrc/feta_gstore.h); the objects
+    # do not remember the flags they were built with: combine with --force
+    flags += os.environ.get('FETA_HIPCC_FLAGS', '').split()
     if report:
         flags.append('-Rpass-analysis=kernel-resource-usage')
     dep_t = max(os.path.getmtime(p) for p in _deps())

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
           t[0] += bv4.x; t[1] += bv4.y; t[2] += bv4.z; t[3] += bv4.w;
           if (node < a.N) {
             const int64_t row = (int64_t)b * a.row_sb + (int64_t)node * a.row_sn;
-            L::st4(gqkv + row * 3 * D + part * D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
+            L::template gst4<kStSaved>(gqkv + row * 3 * D + part * D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
           }
           if (part == 0) {
             qs[nt] = L::mk(t[0] * a.scale, t[1] * a.scale, t[2] * a.scale, t[3] * a.scale);
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
             const int nd = 16 * nt + 4 * g + r;
             if (nd < a.N) {
               const int64_t row = (int64_t)b * a.row_sb + (int64_t)nd * a.row_sn;
-              L::st1(gqkv + row * 3 * D + 2 * D + DH * h + lq, t[r]);
+              L::template gst1<kStSaved>(gqkv + row * 3 * D + 2 * D + DH * h + lq, t[r]);
             }
             if (nd >= n) t[r] = 0.0f;  // padded keys carry no value
           }
@@ -366,8 +366,8 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
     const int q = 16 * qb + lq;
     if (g == 0 && q < a.N) {
       float* st = a.attn_stats + ((int64_t)bh * a.N + q) * 2;
-      st[0] = mx[qb];
-      st[1] = zs[qb];
+      gst1<kStSaved>(st, mx[qb]);
+      gst1<kStSaved>(st + 1, zs[qb]);
     }
   }
 #pragma unroll
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
       float* dst = a.attn + ((int64_t)bh * a.N + 16 * qb) * a.N;
       for (int i = lane; i < rows * a.N; i += 64) {
         const int qq = i / a.N, kk = i - qq * a.N;
-        dst[i] = stg[qq * KP + kk];
+        gst1<kStSaved>(dst + i, stg[qq * KP + kk]);
       }
       wave_lds_sync();
     }
@@ -412,13 +412,13 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
     if (node < a.N) {
       const int64_t row = (int64_t)b * a.row_sb + (int64_t)node * a.row_sn;
       const Vec ov = L::ldv(Os + node * P + L::VEC * q);
-      L::stv(gout + row * D + L::VEC * q, ov);
+      L::template gstv<kStSaved>(gout + row * D + L::VEC * q, ov);
       if (a.out_f32 != nullptr) {   // the same rows as fp32: operand of the fp32 filter stage behind a bf16 stack
         float f[L::VEC];
         L::unpack(ov, f);
 #pragma unroll
         for (int e = 0; e < L::VEC; e += 4)
-          *reinterpret_cast<float4*>(a.out_f32 + row * D + L::VEC * q + e) = make_float4(f[e], f[e + 1], f[e + 2], f[e + 3]);
+          gst4<kStSaved>(a.out_f32 + row * D + L::VEC * q + e, f[e], f[e + 1], f[e + 2], f[e + 3]);
       }
     }
   }
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
       L::ld4(Xs + node * P + o0, res);
       float v[4] = {(t[0] + bo.x) * rs + res[0], (t[1] + bo.y) * rs + res[1], (t[2] + bo.z) * rs + res[2],
                     (t[3] + bo.w) * rs + res[3]};
-      if (rok) L::st4(gy + row * D + o0, v[0], v[1], v[2], v[3]);
+      if (rok) L::template gst4<kStHandoff>(gy + row * D + o0, v[0], v[1], v[2], v[3]);
       if (a.y_stats != nullptr) {   // (NULL: LayerNorm stack - nobody needs column statistics)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -457,9 +457,9 @@ __global__ __launch_bounds__(kRowThreads) void attn_block_fwd_kernel(BlockArgs a
     }
     if (lq == 0 && a.y_stats != nullptr) {
       float* st = a.y_stats + (int64_t)b * 2 * D;
-      *reinterpret_cast<float4*>(st + o0) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-      *reinterpret_cast<float4*>(st + D + o0) = make_float4(s2[0], s2[1], s2[2], s2[3]);
-      if (b == 0) *reinterpret_cast<float4*>(a.y_stats + (int64_t)a.B * 2 * D + o0) = ks;   // row B: the shift
+      gst4<kStHandoff>(st + o0, s1[0], s1[1], s1[2], s1[3]);
+      gst4<kStHandoff>(st + D + o0, s2[0], s2[1], s2[2], s2[3]);
+      if (b == 0) gst4<kStHandoff>(a.y_stats + (int64_t)a.B * 2 * D + o0, ks.x, ks.y, ks.z, ks.w);   // row B: the shift
     }
   }
   }  // graphs of this workgroup
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
         t[0] += binq.x; t[1] += binq.y; t[2] += binq.z; t[3] += binq.w;
         if (node < a.N) {
           const int64_t row = (int64_t)b * a.row_sb + (int64_t)node * a.row_sn;
-          L::st4(gqkv + row * 3 * D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
+          L::template gst4<kStSaved>(gqkv + row * 3 * D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
         }
         qs[nt / S] = L::mk(t[0] * a.scale, t[1] * a.scale, t[2] * a.scale, t[3] * a.scale);
       }
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
           t[0] += bink.x; t[1] += bink.y; t[2] += bink.z; t[3] += bink.w;
           if (!a.tie_qk && node < a.N && (nt % WGS) == w) {
             const int64_t row = (int64_t)b * a.row_sb + (int64_t)node * a.row_sn;
-            L::st4(gqkv + row * 3 * D + D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
+            L::template gst4<kStSaved>(gqkv + row * 3 * D + D + DH * h + 4 * g, t[0], t[1], t[2], t[3]);
           }
           kk = L::mk(t);
         }
@@ -753,7 +753,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
             const int nd = 16 * nt + 4 * g + r;
             if (nd < a.N && (nt % WGS) == w) {
               const int64_t row = (int64_t)b * a.row_sb + (int64_t)nd * a.row_sn;
-              L::st1(gqkv + row * 3 * D + 2 * D + DH * h + lq, t[r]);
+              L::template gst1<kStSaved>(gqkv + row * 3 * D + 2 * D + DH * h + lq, t[r]);
             }
             if (nd >= n) t[r] = 0.0f;  // padded keys carry no value
           }
@@ -836,8 +836,8 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
     const int qb = slot + S * i, q = 16 * qb + lq;
     if (g == 0 && qb < NT && q < a.N) {
       float* st = a.attn_stats + ((int64_t)bh * a.N + q) * 2;
-      st[0] = mx[i];
-      st[1] = zs[i];
+      gst1<kStSaved>(st, mx[i]);
+      gst1<kStSaved>(st + 1, zs[i]);
     }
   }
 #pragma unroll
@@ -874,7 +874,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
       float* dst = a.attn + ((int64_t)bh * a.N + 16 * qb) * a.N;
       for (int j = lane; j < rows * a.N; j += 64) {
         const int qq = j / a.N, kk = j - qq * a.N;
-        dst[j] = stg[qq * KP + kk];
+        gst1<kStSaved>(dst + j, stg[qq * KP + kk]);
       }
       wave_lds_sync();
     }
@@ -946,8 +946,8 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
     const int qb = slot + S * i, q = 16 * qb + lq;
     if (g == 0 && qb < NT && q < a.N) {
       float* st = a.attn_stats + ((int64_t)bh * a.N + q) * 2;
-      st[0] = mx[i];
-      st[1] = zs[i];
+      gst1<kStSaved>(st, mx[i]);
+      gst1<kStSaved>(st + 1, zs[i]);
     }
   }
 #pragma unroll
@@ -987,7 +987,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
       float* dst = a.attn + ((int64_t)bh * a.N + 16 * qb) * a.N;
       for (int j = lane; j < rows * a.N; j += 64) {
         const int qq = j / a.N, kk = j - qq * a.N;
-        dst[j] = stg[qq * KP + kk];
+        gst1<kStSaved>(dst + j, stg[qq * KP + kk]);
       }
       wave_lds_sync();
     }
@@ -1008,13 +1008,13 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
     if (node < a.N && (((node >> 4) & (S - 1)) >> 1) == w) {
       const int64_t row = (int64_t)b * a.row_sb + (int64_t)node * a.row_sn;
       const Vec ov = L::ldv(Os + node * P + L::VEC * q);
-      L::stv(gout + row * D + L::VEC * q, ov);
+      L::template gstv<kStSaved>(gout + row * D + L::VEC * q, ov);
       if (a.out_f32 != nullptr) {
         float f[L::VEC];
         L::unpack(ov, f);
 #pragma unroll
         for (int e = 0; e < L::VEC; e += 4)
-          *reinterpret_cast<float4*>(a.out_f32 + row * D + L::VEC * q + e) = make_float4(f[e], f[e + 1], f[e + 2], f[e + 3]);
+          gst4<kStSaved>(a.out_f32 + row * D + L::VEC * q + e, f[e], f[e + 1], f[e + 2], f[e + 3]);
       }
     }
   }
@@ -1040,7 +1040,7 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
       L::ld4(Xs + node * P + o0, res);
       float v[4] = {(t[0] + bo.x) * rs + res[0], (t[1] + bo.y) * rs + res[1], (t[2] + bo.z) * rs + res[2],
                     (t[3] + bo.w) * rs + res[3]};
-      if (rok) L::st4(gy + row * D + o0, v[0], v[1], v[2], v[3]);
+      if (rok) L::template gst4<kStHandoff>(gy + row * D + o0, v[0], v[1], v[2], v[3]);
       if (a.y_stats != nullptr) {   // (NULL: LayerNorm stack - nobody needs column statistics)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1065,12 +1065,12 @@ __global__ __launch_bounds__(kBlk8Threads) void attn_block_fwd8_kernel(BlockArgs
       const float* e = sx + (4 * h + g) * 8;
       const float4 t1 = *reinterpret_cast<const float4*>(e), t2 = *reinterpret_cast<const float4*>(e + 4);
       float* st = a.y_stats + ((int64_t)b0 * WGS + w) * 2 * D;
-      *reinterpret_cast<float4*>(st + o0) = make_float4(s1[0] + t1.x, s1[1] + t1.y, s1[2] + t1.z, s1[3] + t1.w);
-      *reinterpret_cast<float4*>(st + D + o0) = make_float4(s2[0] + t2.x, s2[1] + t2.y, s2[2] + t2.z, s2[3] + t2.w);
+      gst4<kStHandoff>(st + o0, s1[0] + t1.x, s1[1] + t1.y, s1[2] + t1.z, s1[3] + t1.w);
+      gst4<kStHandoff>(st + D + o0, s2[0] + t2.x, s2[1] + t2.y, s2[2] + t2.z, s2[3] + t2.w);
       if (b0 == 0 && w == 0) {   // the shift row, behind the gp * WGS partial rows
         float4 ks = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (a.y_shift != nullptr) ks = *reinterpret_cast<const float4*>(a.y_shift + o0);
-        *reinterpret_cast<float4*>(a.y_stats + (int64_t)gp * WGS * 2 * D + o0) = ks;
+        gst4<kStHandoff>(a.y_stats + (int64_t)gp * WGS * 2 * D + o0, ks.x, ks.y, ks.z, ks.w);
       }
     }
   }

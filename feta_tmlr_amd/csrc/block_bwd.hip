@@ -66,9 +66,12 @@ __device__ unsigned int feta_bbwd_launch;
 // One element of a workgroup's partial row: the first graph it walks stores, every later one adds.  The add is a
 // no-return float atomic - not for atomicity (only this thread ever touches the element, in program order) but because
 // it has no result: a load-add-store would give the scheduler 40 independent loads per lane to hoist above the
-// attention phase (the kernel spilled 0.5 - 1 KB per lane that way).
+// attention phase (the kernel spilled 0.5 - 1 KB per lane that way).  POL: the policy of the first store (feta_gstore.h)
+// - the partial rows' in the one-graph forms, where nothing reads the row before the end of the step; plain in the LOOP
+// forms, whose adds work on the row in the workgroup's own L2.
+template <int POL>
 __device__ __forceinline__ void acc_to(float* p, float v, bool first) {
-  if (first) *p = v;
+  if (first) gst1<POL>(p, v);
   else atomicAdd(p, v);
 }
 
@@ -92,6 +95,7 @@ static_assert(kDwThreads == kBbThreads, "the dW role is written for the workgrou
 template <class T, int NT, bool SPLIT, bool LOOP, bool TWO, bool DW = false>
 __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, ColsumPlan sums, int main_grid, LinDwHost<DW> dw) {
   static_assert(!DW || (std::is_same<T, float>::value && !SPLIT && !LOOP), "the dW role: fp32, one workgroup per graph");
+  constexpr int kPr = LOOP ? kStPlain : kStPartial;   // first store of a partial-row element (acc_to)
   // Workgroups beyond main_grid reduce column sums (feta_colsum.h): the LAST launch of a stack's backward runs one workgroup
   // per graph - half the chip at the BASELINE batch - while every split-K partial of the layers behind it, and of this
   // layer's feed-forward half, is already complete; reduced here, the stack's final reduction launch is left with this
@@ -402,14 +406,14 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
       float sv = 0.0f;
 #pragma unroll
       for (int w8 = 0; w8 < 8; ++w8) sv += DBO[w8 * D + tid];
-      acc_to(prow + D * D + tid, sv, first);
+      acc_to<kPr>(prow + D * D + tid, sv, first);
     }
     if (gln && hp == 0 && tid >= D && tid < 3 * D) {   // [dgamma1 | dbeta1] behind db_in
       const int which = (tid - D) / D, c = (tid - D) % D;
       float sv = 0.0f;
 #pragma unroll
       for (int w8 = 0; w8 < 8; ++w8) sv += DGL[(w8 * 2 + which) * D + c];
-      acc_to(prow + 4 * D * D + 4 * D + which * D + c, sv, first);
+      acc_to<kPr>(prow + 4 * D * D + 4 * D + which * D + c, sv, first);
     }
 
     // ---- dconcat^T tiles (c = 16h + 4g + r, row = 16 rt + lq) = sum_o W_out[o][c] (degree g1)[row][o] (+ dout2) ----
@@ -697,7 +701,7 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
 #pragma unroll
         for (int r = 0; r < 4; ++r)
         {
-          acc_to(prow + (int64_t)(16 * ot + 4 * g + r) * D + 16 * (SPLIT ? 2 * hp + i : i) + lq, aWo[i][r], first);
+          acc_to<kPr>(prow + (int64_t)(16 * ot + 4 * g + r) * D + 16 * (SPLIT ? 2 * hp + i : i) + lq, aWo[i][r], first);
         }
     }
     BB_STAMP(4);
@@ -762,7 +766,7 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
       L::ld4(Gt + rowl * P + 16 * ktile + 4 * g, res);
       const float v[4] = {acc[0] + resw * res[0], acc[1] + resw * res[1], acc[2] + resw * res[2], acc[3] + resw * res[3]};
       const bool rok = rowl < a.N;
-      if (rok) L::st4(dxo + grow(rowl) * D + 16 * ktile + 4 * g, v[0], v[1], v[2], v[3]);
+      if (rok) L::template gst4<kStHandoff>(dxo + grow(rowl) * D + 16 * ktile + 4 * g, v[0], v[1], v[2], v[3]);
       if (want_sums) {
         float xx[4];
         L::ld4(X0 + rowl * P + 16 * ktile + 4 * g, xx);
@@ -796,16 +800,16 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
         if ((wv >> 2) == 0 && lq == 0) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            a.sum_out[((int64_t)blockIdx.x * 2 + 0) * D + 16 * ktile + 4 * g + r] = s1v[r] + red[(ktile * 2 + 0) * 16 + 4 * g + r];
-            a.sum_out[((int64_t)blockIdx.x * 2 + 1) * D + 16 * ktile + 4 * g + r] = s2v[r] + red[(ktile * 2 + 1) * 16 + 4 * g + r];
+            gst1<kStHandoff>(a.sum_out + ((int64_t)blockIdx.x * 2 + 0) * D + 16 * ktile + 4 * g + r, s1v[r] + red[(ktile * 2 + 0) * 16 + 4 * g + r]);
+            gst1<kStHandoff>(a.sum_out + ((int64_t)blockIdx.x * 2 + 1) * D + 16 * ktile + 4 * g + r, s2v[r] + red[(ktile * 2 + 1) * 16 + 4 * g + r]);
           }
         }
       } else if (lq == 0 && (!LOOP || b + nwg >= a.B)) {   // (the last graph of this workgroup: sum1 / sum2 ran over all)
         const int64_t prow2 = (int64_t)blockIdx.x * 2 + (wv >> 2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          a.sum_out[(prow2 * 2 + 0) * D + 16 * ktile + 4 * g + r] = s1v[r];
-          a.sum_out[(prow2 * 2 + 1) * D + 16 * ktile + 4 * g + r] = s2v[r];
+          gst1<kStHandoff>(a.sum_out + (prow2 * 2 + 0) * D + 16 * ktile + 4 * g + r, s1v[r]);
+          gst1<kStHandoff>(a.sum_out + (prow2 * 2 + 1) * D + 16 * ktile + 4 * g + r, s2v[r]);
         }
       }
     }
@@ -842,7 +846,7 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
 #pragma unroll
       for (int r = 0; r < 4; ++r)
       {
-        acc_to(pWi + (int64_t)(64 * wi_part(i) + 16 * wi_head(i) + 4 * g + r) * D + 16 * ktile + lq, aWi[i][r], first);
+        acc_to<kPr>(pWi + (int64_t)(64 * wi_part(i) + 16 * wi_head(i) + 4 * g + r) * D + 16 * ktile + lq, aWi[i][r], first);
       }
     // db_in from the fp32 column sums the attention waves left (DBS: written before two barriers ago)
     if (tid < 3 * D) {
@@ -851,10 +855,10 @@ __global__ __launch_bounds__(kBbThreads) void attn_block_bwd_kernel(BwdArgs a, C
       if (SPLIT) {
         if ((hh >> 1) == hp) {
           const int wa = (hh & 1) + 2 * rl;
-          pbi[tid] = DBS[(wa * 2 + which) * 16 + c] + DBS[((wa + 4) * 2 + which) * 16 + c];   // (one graph per pair)
+          gst1<kStPartial>(pbi + tid, DBS[(wa * 2 + which) * 16 + c] + DBS[((wa + 4) * 2 + which) * 16 + c]);   // (one graph per pair)
         }
       } else {
-        acc_to(pbi + tid, DBS[((hh + 4 * rl) * 2 + which) * 16 + c], first);
+        acc_to<kPr>(pbi + tid, DBS[((hh + 4 * rl) * 2 + which) * 16 + c], first);
       }
     }
     b += nwg;

@@ -8,6 +8,7 @@
 
 #include "feta_abi_common.h"
 #include <feta_device.h>
+#include "feta_gstore.h"
 
 namespace feta {
 
@@ -79,7 +80,7 @@ __device__ __forceinline__ void coeff_fwd_body(
       float c = 0.0f;
       if (col < n) c = ((ps[col] + ps[64 + col]) + (ps[128 + col] + ps[192 + col])) * dis[col];
       cjs[col] = c;
-      if (cs == 0) cj_out[(int64_t)blk * N + col] = c;
+      if (cs == 0) gst1<kStSaved>(cj_out + (int64_t)blk * N + col, c);
     }
     __syncthreads();
   } else if (stage == 2) {
@@ -160,7 +161,7 @@ __device__ __forceinline__ void coeff_fwd_body(
         c = (c + diag0 * dj) * dj;
       }
       cjs[j] = c;
-      if (cs == 0) cj_out[(int64_t)blk * N + j] = c;
+      if (cs == 0) gst1<kStSaved>(cj_out + (int64_t)blk * N + j, c);
     }
     __syncthreads();
   } else {
@@ -199,7 +200,7 @@ __device__ __forceinline__ void coeff_fwd_body(
         c *= dis[j];
       }
       cjs[j] = c;
-      if (cs == 0) cj_out[(int64_t)blk * N + j] = c;
+      if (cs == 0) gst1<kStSaved>(cj_out + (int64_t)blk * N + j, c);
     }
     __syncthreads();
   }
@@ -216,7 +217,7 @@ __device__ __forceinline__ void coeff_fwd_body(
       const float sc = s[c], bc = gbias[c];
       float acc = 0.0f;
       for (int i = 0; i < n; ++i) acc += fast_tanh(cjs[i] * sc + bc);
-      pooled[(int64_t)blk * C + c] = acc * inv_n;
+      gst1<kStSaved>(pooled + (int64_t)blk * C + c, acc * inv_n);
     }
     return;
   }
@@ -238,7 +239,7 @@ __device__ __forceinline__ void coeff_fwd_body(
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + k * TH;
-      if (c < cend) pooled[(int64_t)blk * C + c] = acc[k] * inv_n;
+      if (c < cend) gst1<kStSaved>(pooled + (int64_t)blk * C + c, acc[k] * inv_n);
     }
   }
 }
@@ -324,8 +325,8 @@ __device__ __forceinline__ void coeff_bwd_body(
     }
   }
   if (c < C) {
-    partial[(int64_t)grp * 2 * C + c] = as;      // [G][2][C]: one colsum reduces both
-    partial[(int64_t)grp * 2 * C + C + c] = ab;
+    gst1<kStPartial>(partial + (int64_t)grp * 2 * C + c, as);      // [G][2][C]: one colsum reduces both
+    gst1<kStPartial>(partial + (int64_t)grp * 2 * C + C + c, ab);
   }
 }
 
@@ -372,8 +373,8 @@ __device__ __forceinline__ void coeff_dsum_body(
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + k * kCoeffThreads;
       if (c < C) {
-        A[(int64_t)blk * C + c] = as[k] * inv_n;
-        Bm[(int64_t)blk * C + c] = ab[k] * inv_n;
+        gst1<kStSaved>(A + (int64_t)blk * C + c, as[k] * inv_n);
+        gst1<kStSaved>(Bm + (int64_t)blk * C + c, ab[k] * inv_n);
       }
     }
   }
@@ -413,8 +414,8 @@ __device__ __forceinline__ void coeff_bwd_saved_body(
     }
   }
   if (c < C) {
-    partial[(int64_t)grp * 2 * C + c] = as;      // [G][2][C], as coeff_bwd_body
-    partial[(int64_t)grp * 2 * C + C + c] = ab;
+    gst1<kStPartial>(partial + (int64_t)grp * 2 * C + c, as);      // [G][2][C], as coeff_bwd_body
+    gst1<kStPartial>(partial + (int64_t)grp * 2 * C + C + c, ab);
   }
 }
 

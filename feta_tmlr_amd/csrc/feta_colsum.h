@@ -10,6 +10,7 @@
 
 #include "feta_abi_common.h"
 #include <feta_device.h>
+#include "feta_gstore.h"
 
 namespace feta {
 
@@ -109,7 +110,7 @@ __device__ __forceinline__ void colsum_role(const ColsumPlan& sg, int tile_id) {
       }
       acc = red[tid % WQ];
     }
-    if (ok && slice == 0) *reinterpret_cast<float4*>(s.out + 4 * (int64_t)c4) = acc;
+    if (ok && slice == 0) gst4<kStPartial>(s.out + 4 * (int64_t)c4, acc.x, acc.y, acc.z, acc.w);
     return;
   }
   // 16 columns x THREADS / 16 row slices, pairwise tree over the slices
@@ -136,7 +137,7 @@ __device__ __forceinline__ void colsum_role(const ColsumPlan& sg, int tile_id) {
   }
   if (col < s.C) {
     const float v = red[lc];
-    if (slice == 0) s.out[col] = v;
+    if (slice == 0) gst1<kStPartial>(s.out + col, v);
     if (s.bcast_out != nullptr)
       for (int r = slice; r < s.bcast_rows; r += SL) s.bcast_out[(int64_t)r * s.C + col] = v;
   }

@@ -130,6 +130,49 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// ---- global stores with a cache policy (feta_gstore.h chooses one per class of tensor) --------------------
+// GLOBAL memory only, 4 / 8 / 16 bytes per lane, naturally aligned.  kStPlain: an ordinary store - the line stays
+// dirty in the XCD's L2 until the end-of-kernel write-back.  kStWt: write-through (`sc1`) - the bytes leave for the
+// memory side while the kernel still runs, the line is dropped from L2; for data nobody reads again in this launch.
+// kStNt: non-temporal (`nt`; NOT write-through, kept for measurements).  <= 8 bytes are relaxed agent-scope atomic
+// stores, which the compiler lowers to global_store_dword / dwordx2 sc1 and schedules like any store; there is no
+// 16-byte atomic, so that width is the instruction itself (s_nop 1: the next instruction may rewrite the data
+// registers, cdna_hip_programming.md 5.7; the compiler does not count it in vmcnt, which only ever makes a wait
+// of its own conservative - nothing waits FOR these stores).
+constexpr int kStPlain = 0, kStWt = 1, kStNt = 2;
+typedef unsigned long long __attribute__((address_space(1)))* feta_gu64;
+typedef unsigned int __attribute__((address_space(1)))* feta_gu32;
+template <int POL>
+__device__ __forceinline__ void gst_b128(void* p, f32x4 v) {
+  if constexpr (POL == kStWt) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+  } else if constexpr (POL == kStNt) {
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
+  } else {
+    *reinterpret_cast<f32x4*>(p) = v;
+  }
+}
+template <int POL>
+__device__ __forceinline__ void gst_b64(void* p, unsigned long long v) {
+  if constexpr (POL == kStWt) {
+    __hip_atomic_store((feta_gu64)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (POL == kStNt) {
+    __builtin_nontemporal_store(v, reinterpret_cast<unsigned long long*>(p));
+  } else {
+    *reinterpret_cast<unsigned long long*>(p) = v;
+  }
+}
+template <int POL>
+__device__ __forceinline__ void gst_b32(void* p, float v) {
+  if constexpr (POL == kStWt) {
+    __hip_atomic_store((feta_gu32)p, __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (POL == kStNt) {
+    __builtin_nontemporal_store(v, reinterpret_cast<float*>(p));
+  } else {
+    *reinterpret_cast<float*>(p) = v;
+  }
+}
+
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 // tanh(x) = 1 - 2 / (1 + e^{2x}): saturates correctly at +-1, absolute error ~1e-7
 __device__ __forceinline__ float fast_tanh(float x) {

@@ -16,6 +16,7 @@
 #pragma once
 #include "feta_abi_common.h"
 #include <feta_device.h>
+#include "feta_gstore.h"
 #include "feta_tiles.h"
 
 namespace feta {
@@ -147,11 +148,8 @@ __device__ __forceinline__ void lin_dw_tile(const LinDwPlan& a, int ti, int tj) 
   float* out = a.dw + (int64_t)(i0 + 32 * iw + 8 * g) * a.K + j0 + 32 * jw + 2 * lq;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float2 v0, v1;
-    v0.x = a00[r]; v0.y = a01[r];
-    v1.x = a10[r]; v1.y = a11[r];
-    *reinterpret_cast<float2*>(out + (int64_t)(2 * r) * a.K) = v0;
-    *reinterpret_cast<float2*>(out + (int64_t)(2 * r + 1) * a.K) = v1;
+    gst2<kStPartial>(out + (int64_t)(2 * r) * a.K, a00[r], a01[r]);
+    gst2<kStPartial>(out + (int64_t)(2 * r + 1) * a.K, a10[r], a11[r]);
   }
   if (a.db != nullptr && tj == 0) {
     // thread (rr = tid / 32, c4 = tid % 32) summed rows rr, rr + 16, ... of columns i0 + 4 c4 ..: the 16 threads that
@@ -164,7 +162,7 @@ __device__ __forceinline__ void lin_dw_tile(const LinDwPlan& a, int ti, int tj) 
       const int c4 = threadIdx.x >> 2, e = threadIdx.x & 3;
       float sv = 0.0f;
       for (int k = 0; k < kDwThreads / 32; ++k) sv += red[(c4 + 32 * k) * 4 + e];
-      a.db[i0 + threadIdx.x] = sv;
+      gst1<kStPartial>(a.db + i0 + threadIdx.x, sv);
     }
   }
 }

@@ -16,6 +16,7 @@
 // feeds to four f32 MFMAs are the four k-consecutive values it feeds to one bf16 MFMA: no operand changes place
 // between the two instantiations (feta_bf16.h makes the same observation for the general kernels).
 #pragma once
+#include "feta_gstore.h"
 #include "feta_tiles.h"
 
 namespace feta {
@@ -76,6 +77,13 @@ struct Lp<float> {
   }
   static __device__ __forceinline__ Vec ldv(const float* p) { return Vec{*reinterpret_cast<const float4*>(p)}; }
   static __device__ __forceinline__ void stv(float* p, const Vec& v) { *reinterpret_cast<float4*>(p) = v.raw; }
+  // the same three stores to GLOBAL memory with a cache policy (feta_gstore.h); st4 / stv / st1 also serve LDS
+  template <int POL>
+  static __device__ __forceinline__ void gst1(float* p, float v) { feta::gst1<POL>(p, v); }
+  template <int POL>
+  static __device__ __forceinline__ void gst4(float* p, float a, float b, float c, float d) { feta::gst4<POL>(p, a, b, c, d); }
+  template <int POL>
+  static __device__ __forceinline__ void gstv(float* p, const Vec& v) { feta::gst4<POL>(p, v.raw.x, v.raw.y, v.raw.z, v.raw.w); }
   static __device__ __forceinline__ void unpack(const Vec& v, float (&f)[VEC]) {
     f[0] = v.raw.x; f[1] = v.raw.y; f[2] = v.raw.z; f[3] = v.raw.w;
   }
@@ -123,6 +131,25 @@ struct Lp<bf16_t> {
   }
   static __device__ __forceinline__ Vec ldv(const bf16_t* p) { return *reinterpret_cast<const Vec*>(p); }
   static __device__ __forceinline__ void stv(bf16_t* p, const Vec& v) { *reinterpret_cast<Vec*>(p) = v; }
+  // GLOBAL stores with a cache policy: 8 and 16 bytes per lane; a lone bf16 is 2 bytes, below the widths worth a
+  // fabric write of their own, and stays plain.  FETA_ST_BF16 = 0 (the default, feta_gstore.h): every store of bf16
+  // storage is plain - with the classes' policies config 5 (B = 1024, bf16) measured 1.2 - 1.3 % slower.
+  static constexpr int pol(int p) { return FETA_ST_BF16 ? p : kStPlain; }
+  template <int POL>
+  static __device__ __forceinline__ void gst1(bf16_t* p, float v) { st1(p, v); }
+  template <int POL>
+  static __device__ __forceinline__ void gst4(bf16_t* p, float a, float b, float c, float d) {
+    const bf16x4_pk t = pack_bf16x4(a, b, c, d);
+    unsigned long long u;
+    __builtin_memcpy(&u, &t, 8);
+    gst_b64<pol(POL)>(p, u);
+  }
+  template <int POL>
+  static __device__ __forceinline__ void gstv(bf16_t* p, const Vec& v) {
+    f32x4 t;
+    __builtin_memcpy(&t, &v, 16);
+    gst_b128<pol(POL)>(p, t);
+  }
   static __device__ __forceinline__ void unpack(const Vec& v, float (&f)[VEC]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(kRowThreads) void ffn_fwd_kernel(FfnArgs a, CoeffFw
     v[2] = fmaxf(v[2] + b1v[t].z, 0.0f);
     v[3] = fmaxf(v[3] + b1v[t].w, 0.0f);
     ho[t] = L::mk(v);   // the accumulator tile of the first product IS the B operand of the second
-    if (rok) L::st4(gh + (int64_t)row * FF + o + 4 * g, v[0], v[1], v[2], v[3]);
+    if (rok) L::template gst4<kStSaved>(gh + (int64_t)row * FF + o + 4 * g, v[0], v[1], v[2], v[3]);
   }
   FFN_STAMP(3);
   // ---- partial y2^T tiles over this half: (output 4g+r, row lq) --------------------------------------
@@ -292,8 +292,8 @@ __global__ __launch_bounds__(kRowThreads) void ffn_fwd_kernel(FfnArgs a, CoeffFw
       v[r] = own + theirs[(t * 4 + r) * 64 + lane] + bb[r] + res;
     }
     if (rok) {
-      if (a.y_f32) *reinterpret_cast<float4*>(a.y + (int64_t)row * D + o2) = make_float4(v[0], v[1], v[2], v[3]);
-      else L::st4(gy + (int64_t)row * D + o2, v[0], v[1], v[2], v[3]);
+      if (a.y_f32) gst4<kStHandoff>(a.y + (int64_t)row * D + o2, v[0], v[1], v[2], v[3]);
+      else L::template gst4<kStHandoff>(gy + (int64_t)row * D + o2, v[0], v[1], v[2], v[3]);
     }
     if (want_stats) {
       const float kk[4] = {ksv[t].x, ksv[t].y, ksv[t].z, ksv[t].w};
@@ -342,16 +342,16 @@ __global__ __launch_bounds__(kRowThreads) void ffn_fwd_kernel(FfnArgs a, CoeffFw
         const int o2 = 16 * (2 * hh + t) + 4 * g;
         const float o0 = vv[t][0] * rstd * lgv[t].x + lbv[t].x, o1 = vv[t][1] * rstd * lgv[t].y + lbv[t].y;
         const float o2v = vv[t][2] * rstd * lgv[t].z + lbv[t].z, o3 = vv[t][3] * rstd * lgv[t].w + lbv[t].w;
-        if (a.y_ln_f32) *reinterpret_cast<float4*>(a.y_ln_out + (int64_t)row * D + o2) = make_float4(o0, o1, o2v, o3);
-        else L::st4(reinterpret_cast<T*>(a.y_ln_out) + (int64_t)row * D + o2, o0, o1, o2v, o3);
+        if (a.y_ln_f32) gst4<kStHandoff>(a.y_ln_out + (int64_t)row * D + o2, o0, o1, o2v, o3);
+        else L::template gst4<kStHandoff>(reinterpret_cast<T*>(a.y_ln_out) + (int64_t)row * D + o2, o0, o1, o2v, o3);
       }
     }
   }
   FFN_STAMP(5);
   }  // row blocks of this workgroup
-  if (want_stats && tid < 2 * D) a.y_stats[(int64_t)blockIdx.x * 2 * D + tid] = tot1[0];
+  if (want_stats && tid < 2 * D) gst1<kStHandoff>(a.y_stats + (int64_t)blockIdx.x * 2 * D + tid, tot1[0]);
   if (want_stats && blockIdx.x == 0 && tid < D)   // row main_grid: the shift these sums are relative to
-    a.y_stats[(int64_t)main_grid * 2 * D + tid] = a.y_shift != nullptr ? a.y_shift[tid] : 0.0f;
+    gst1<kStHandoff>(a.y_stats + (int64_t)main_grid * 2 * D + tid, a.y_shift != nullptr ? a.y_shift[tid] : 0.0f);
 }
 
 template <class T, int FF>

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(kRowThreads) void ffn_bwd_kernel(FfnGradArgs a, Ffn
         const float v[4] = {acc[0] + res[0], acc[1] + res[1], acc[2] + res[2], acc[3] + res[3]};
         const int row = r0 + 16 * rt + lq;
         const bool rok = row < a.M;
-        if (rok) L::st4(gdx + (int64_t)row * D + 16 * w + 4 * g, v[0], v[1], v[2], v[3]);
+        if (rok) L::template gst4<kStHandoff>(gdx + (int64_t)row * D + 16 * w + 4 * g, v[0], v[1], v[2], v[3]);
         if (want_sums) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -352,8 +352,8 @@ __global__ __launch_bounds__(kRowThreads) void ffn_bwd_kernel(FfnGradArgs a, Ffn
       for (int r = 0; r < 4; ++r) {
         const float s1 = row16_sum(sum1[r]), s2 = row16_sum(sum2[r]);
         if (lq == 0) {
-          a.sum_out[((int64_t)xblk * 2 + 0) * D + 16 * w + 4 * g + r] = s1;
-          a.sum_out[((int64_t)xblk * 2 + 1) * D + 16 * w + 4 * g + r] = s2;
+          gst1<kStHandoff>(a.sum_out + ((int64_t)xblk * 2 + 0) * D + 16 * w + 4 * g + r, s1);
+          gst1<kStHandoff>(a.sum_out + ((int64_t)xblk * 2 + 1) * D + 16 * w + 4 * g + r, s2);
         }
       }
     }
@@ -497,8 +497,8 @@ __global__ __launch_bounds__(kRowThreads) void ffn_bwd_kernel(FfnGradArgs a, Ffn
   for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      pW2[(int64_t)(16 * w + 4 * g + r) * FF + c0 + 16 * ct + lq] = aW2[ct][r];
-      pW1[(int64_t)(c0 + 16 * ct + 4 * g + r) * D + 16 * w + lq] = aW1[ct][r];
+      gst1<kStPartial>(pW2 + (int64_t)(16 * w + 4 * g + r) * FF + c0 + 16 * ct + lq, aW2[ct][r]);
+      gst1<kStPartial>(pW1 + (int64_t)(c0 + 16 * ct + 4 * g + r) * D + 16 * w + lq, aW1[ct][r]);
     }
   // db2 | db1: the per-thread fp32 column sums meet in LDS (the tiles are no longer needed), fixed order
   __syncthreads();
@@ -527,21 +527,21 @@ __global__ __launch_bounds__(kRowThreads) void ffn_bwd_kernel(FfnGradArgs a, Ffn
     const int c4 = tid / VEC, e = tid % VEC;
     float sv = 0.0f;
     for (int k = 0; k < kRowThreads / RV; ++k) sv += red2[(c4 + RV * k) * VEC + e];
-    pb2[tid] = sv;
+    gst1<kStPartial>(pb2 + tid, sv);
     if (gln) {   // [dgamma2 | dbeta2] behind db1
       float sg = 0.0f, sb = 0.0f;
       for (int k = 0; k < kRowThreads / RV; ++k) {
         sg += red3[(c4 + RV * k) * VEC + e];
         sb += red4[(c4 + RV * k) * VEC + e];
       }
-      pb1[FF + tid] = sg;
-      pb1[FF + D + tid] = sb;
+      gst1<kStPartial>(pb1 + FF + tid, sg);
+      gst1<kStPartial>(pb1 + FF + D + tid, sb);
     }
   }
   if (tid < kFbSlice) {
     const int t = tid >> 4, cc = tid & 15;
-    pb1[c0 + tid] = (red1[(0 * 2 + t) * 16 + cc] + red1[(1 * 2 + t) * 16 + cc]) +
-                    (red1[(2 * 2 + t) * 16 + cc] + red1[(3 * 2 + t) * 16 + cc]);
+    gst1<kStPartial>(pb1 + c0 + tid, (red1[(0 * 2 + t) * 16 + cc] + red1[(1 * 2 + t) * 16 + cc]) +
+                                         (red1[(2 * 2 + t) * 16 + cc] + red1[(3 * 2 + t) * 16 + cc]));
   }
 }
 

@@ -1634,10 +1634,10 @@ __global__ __launch_bounds__(256) void spec_cat_fwd_graph_kernel(FilterArgs a, C
   for (int i = 0; i < NT_MAX; ++i) {
     const int idx = tid + 256 * i, node = idx >> 4, q = idx & 15;
     if (node < a.N) {
-      *reinterpret_cast<float4*>(tok_row(a.y, a.ysb, a.ysn, b, node, 0, DH) + 4 * q) =
-          *reinterpret_cast<const float4*>(Xs + node * XP + 4 * q);
-      *reinterpret_cast<float4*>(tok_row(c.out, a.ysb, a.ysn, b, node, 0, DH) + 4 * q) =
-          *reinterpret_cast<const float4*>(Ys + node * XP + 4 * q);
+      const float4 fv = *reinterpret_cast<const float4*>(Xs + node * XP + 4 * q);
+      const float4 ov = *reinterpret_cast<const float4*>(Ys + node * XP + 4 * q);
+      gst4<kStHandoff>(tok_row(a.y, a.ysb, a.ysn, b, node, 0, DH) + 4 * q, fv.x, fv.y, fv.z, fv.w);
+      gst4<kStHandoff>(tok_row(c.out, a.ysb, a.ysn, b, node, 0, DH) + 4 * q, ov.x, ov.y, ov.z, ov.w);
     }
   }
 }
@@ -1925,6 +1925,9 @@ __global__ __launch_bounds__(256) void spec_cat_bwd_graph_kernel(FilterArgs a, C
     dbs += shfl_xor(dbs, 16);
     dbs += shfl_xor(dbs, 32);
     // (TWO: item (b, head 2h + (lq >> 3)), column lq & 7 of its [8] row - the same address, b * 64 + col)
+    // (every store of this kernel is a plain store: with write-through stores (feta_gstore.h) for the partial row, dcoeff
+    // and dbias_part the <3, 1, 4> instantiations - the headline's - took 224 VGPRs instead of 184, one wave per SIMD
+    // instead of two)
     if (g == 0) a.dbias_part[TWO ? (int64_t)b * D + col : (int64_t)item * DH + lq] = dbs;
   }
 

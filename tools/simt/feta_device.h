@@ -168,6 +168,15 @@ inline void wave_lds_sync() { simt::wave_barrier(); }
 
 inline void lds_barrier() { simt::block_barrier(); }
 
+// global stores with a cache policy: the emulation has no caches, every policy is the plain store
+constexpr int kStPlain = 0, kStWt = 1, kStNt = 2;
+template <int POL>
+inline void gst_b128(void* p, f32x4 v) { memcpy(p, &v, 16); }
+template <int POL>
+inline void gst_b64(void* p, unsigned long long v) { memcpy(p, &v, 8); }
+template <int POL>
+inline void gst_b32(void* p, float v) { memcpy(p, &v, 4); }
+
 inline float fast_exp(float x) { return expf(x); }
 inline float fast_tanh(float x) { return 1.0f - 2.0f / (1.0f + expf(2.0f * x)); }
 inline float fast_rcp(float x) { return 1.0f / x; }
