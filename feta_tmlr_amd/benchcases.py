@@ -123,7 +123,7 @@ def stack_layer_cases(abi, st, dev, b, n, d, heads, ff, pe, n_real, last_layer_a
         if _F.USE_COEFF_DSUM and n <= 64 and heads == 4 and heads * b <= _F.COEFF_ROLE_MAX_BLOCKS:
             # ... in its saved form where the step takes it (the tanh pass rode in the filter stage's forward launch:
             # feta_ffn_bwd_coeff_saved - a multiply-and-column-sum in trailing workgroups; 4 heads only, as
-            # functional.FilterCoefficientsFn asks for it); the case keeps its name
+            # functional._coeff_forward asks for it); the case keeps its name
             cgrp = abi.coeff_bwd_saved_groups(b, heads)
             brole = _F.CoeffSavedReq(rnd(heads * b, cgen), rnd(heads * b, cgen), rnd(heads * b, cgen), new(cgrp, 2, cgen),
                                      b, heads)

@@ -93,109 +93,98 @@ class AttentionCoreFn(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None, None, None
 
 
+def _coeff_forward(abi, stream, attn, n_real, gcn_weight, gcn_bias, pending=None):
+    """The coefficient generator's forward (feta_colsum, feta_coeff_fwd) -> (pooled [H*B, C], cj, s, gcn bias) - or
+    whatever of it the layer stack's launches already ran (pending: the forward hand-over of PendingSums)."""
+    attn = attn.contiguous()
+    b, h, n, _ = attn.shape
+    c = gcn_weight.shape[1]
+    dev = attn.device
+    if pending is not None and pending.s is not None:
+        s = pending.s                 # requested by the encoder ...
+        left = pending.take_fwd()     # ... and computed inside the layer stack's first launch, or not yet
+        if left:
+            abi.colsum_multi(left, stream)
+        pending.s = None
+    else:
+        s = torch.empty(c, dtype=torch.float32, device=dev)
+        abi.colsum(gcn_weight.contiguous(), s, stream)
+    gb = gcn_bias.contiguous()
+    if pending is not None and pending.coeff_fwd_out is not None:
+        cj, pooled = pending.coeff_fwd_out      # ran in the launch of the last layer's feed-forward half
+        pending.coeff_fwd_out = None
+    else:
+        cj = torch.empty((h * b, n), dtype=torch.float32, device=dev)
+        pooled = torch.empty((h * b, c), dtype=torch.float32, device=dev)
+        abi.coeff_fwd(attn, n_real, s, gb, cj, pooled, stream)
+    if pending is not None:
+        pending.coeff_fwd_req = None
+    return pooled, cj, s, gb
+
+
+def _coeff_backward(abi, stream, cj, n_real, s, gb, dims, dpooled, saved=None, pending=None, params=(), waiting=(),
+                    owners=()):
+    """The coefficient generator's backward -> (dW, db) of the GCN parameters.  dims = (B, N, H, rows of gcn.weight).
+    saved = (A, Bm): the tanh pass already ran (feta_coeff_dsum) and what is left is a multiply-and-column-sum; else the
+    kernel recomputes the tanh.  waiting / owners: column sums (and the gradients they complete) that earlier steps of the
+    same backward left for this step's reduction launch.  pending with the stack's backward still to come in this pass and
+    params = (gcn.weight, gcn.bias) untouched: kernel and sums are left to the stack's launches."""
+    b, n, h, rows = dims
+    c = s.shape[0]
+    dsdb = torch.empty((2, c), dtype=torch.float32, device=cj.device)   # contiguous: one reduction
+    ds, db = dsdb[0], dsdb[1]
+    # s = 1^T W  =>  every row of dW equals ds: the reduction launch writes the dense rows itself (an
+    # expanded view would be copied into a dense .grad by autograd: one more 4 MB kernel per step)
+    dw = torch.empty((rows, c), dtype=torch.float32, device=cj.device)
+    dpc = dpooled.contiguous()
+    if saved is not None and torch.is_grad_enabled():
+        saved = None        # a backward under grad mode (create_graph=True): the recompute form, as it stands
+    if saved is not None:
+        A, Bm = saved
+        partial = torch.empty((abi.coeff_bwd_saved_groups(b, h), 2, c), dtype=torch.float32, device=cj.device)
+        req = CoeffSavedReq(dpc, A, Bm, partial, b, h)
+        run = lambda ds_, db_, **kw: abi.coeff_bwd_saved(dpc, A, Bm, partial, ds_, db_, b, h, stream, **kw)
+    else:
+        partial = torch.empty((abi.coeff_bwd_groups(b, h), 2, c), dtype=torch.float32, device=cj.device)
+        req = (cj, n_real, s, gb, dpc, partial, b, n, h)
+        run = lambda ds_, db_, **kw: abi.coeff_bwd(cj, n_real, s, gb, dpc, partial, ds_, db_, b, n, h, stream, **kw)
+    p2 = partial.view(-1, 2 * c)
+    if pending is not None and pending.stack_armed and not pending.stack_done and PendingSums.untouched(*params):
+        # the layer stack's backward comes after this node: its first launch carries the kernel in trailing workgroups
+        # (feta_ffn_bwd_coeff[_saved]), its reduction launch the sums
+        pending.coeff_bwd_req = req
+        for item in waiting:
+            pending.add(*item)
+        pending.owners += owners
+        pending.add(p2[:, :c], ds, dw, owners=[(params[0], dw)])
+        pending.add(p2[:, c:], db, owners=[(params[1], db)])
+    elif waiting:
+        # ONE reduction launch for this step's partials and every column sum the steps before it left
+        run(None, None)
+        abi.colsum_multi([(p2[:, :c], ds, dw), (p2[:, c:], db)] + list(waiting), stream)
+    else:
+        run(ds, db, dw_dense=dw)
+    return dw, db
+
+
 class FilterCoefficientsFn(torch.autograd.Function):
     """attn [B,H,N,N] (detached) + GCN parameters -> pooled [H*B, C]
     (transformer/models.py:240-283 collapsed; C ABI: feta_colsum, feta_coeff_fwd/bwd)."""
 
     @staticmethod
-    def forward(ctx, attn, n_real, gcn_weight, gcn_bias, pending=None):
+    def forward(ctx, attn, n_real, gcn_weight, gcn_bias):
         abi, stream = _lib.backend(attn, gcn_weight)
-        ctx.pending = pending
-        ctx.params = (gcn_weight, gcn_bias)
-        if pending is not None and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]):
-            pending.coeff_armed = True      # this node's backward is the last of the filter stage: it flushes
-        attn = attn.contiguous()
-        b, h, n, _ = attn.shape
-        c = gcn_weight.shape[1]
-        dev = attn.device
-        if pending is not None and pending.s is not None:
-            s = pending.s                 # requested by the encoder ...
-            left = pending.take_fwd()     # ... and computed inside the layer stack's first launch, or not yet
-            if left:
-                abi.colsum_multi(left, stream)
-            pending.s = None
-        else:
-            s = torch.empty(c, dtype=torch.float32, device=dev)
-            abi.colsum(gcn_weight.contiguous(), s, stream)
-        gb = gcn_bias.contiguous()
-        if pending is not None and pending.coeff_fwd_out is not None:
-            cj, pooled = pending.coeff_fwd_out      # ran in the launch of the last layer's feed-forward half
-            pending.coeff_fwd_out = None
-        else:
-            cj = torch.empty((h * b, n), dtype=torch.float32, device=dev)
-            pooled = torch.empty((h * b, c), dtype=torch.float32, device=dev)
-            abi.coeff_fwd(attn, n_real, s, gb, cj, pooled, stream)
-        if pending is not None:
-            pending.coeff_fwd_req = None
-            pending.coeff_dsum_req = pending.coeff_dsum_out = None
-            if USE_COEFF_DSUM and pending.coeff_armed and n <= 64 and h == 4 and h * b <= COEFF_ROLE_MAX_BLOCKS:
-                # this node's backward will run: the filter stage's forward launch, which comes next and leaves most of the
-                # chip idle, may compute the tanh part of it (A, Bm: feta_coeff_dsum) - PendingSums.coeff_dsum_role.  4 heads
-                # only: the launch that carries the role (feta_spec_filter_cat_fwd_coeff) has no 8-head form
-                pending.coeff_dsum_req = (cj.detach(), n_real, s.detach(), gb.detach(), b, n, h)
+        pooled, cj, s, gb = _coeff_forward(abi, stream, attn, n_real, gcn_weight, gcn_bias)
         ctx.save_for_backward(cj, n_real, s, gb)
-        ctx.dims = (b, n, h, gcn_weight.shape[0])
+        ctx.dims = (attn.shape[0], attn.shape[2], attn.shape[1], gcn_weight.shape[0])
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
         cj, n_real, s, gb = ctx.saved_tensors
-        b, n, h, rows = ctx.dims
         abi, stream = _lib.backend(cj)
-        c = s.shape[0]
-        dsdb = torch.empty((2, c), dtype=torch.float32, device=cj.device)   # contiguous: one reduction
-        ds, db = dsdb[0], dsdb[1]
-        # s = 1^T W  =>  every row of dW equals ds: the reduction launch writes the dense rows itself (an
-        # expanded view would be copied into a dense .grad by autograd: one more 4 MB kernel per step)
-        dw = torch.empty((rows, c), dtype=torch.float32, device=cj.device)
-        pend = ctx.pending
-        saved = None
-        if pend is not None:
-            saved, pend.coeff_dsum_out = pend.coeff_dsum_out, None
-            pend.coeff_dsum_req = None
-        if saved is not None and torch.is_grad_enabled():
-            saved = None        # a backward under grad mode (create_graph=True): the earlier form, as it stands
-        if saved is not None:
-            # A / Bm exist (the filter stage's forward launch carried the tanh pass): what is left is a multiply-and-column-
-            # sum - as trailing workgroups of the stack's first backward launch, or on its own
-            A, Bm = saved
-            sg = abi.coeff_bwd_saved_groups(b, h)
-            partial = torch.empty((sg, 2, c), dtype=torch.float32, device=cj.device)
-            dpc = dpooled.contiguous()
-            if (pend.stack_armed and not pend.stack_done and PendingSums.untouched(*ctx.params)):
-                pend.coeff_bwd_req = CoeffSavedReq(dpc, A, Bm, partial, b, h)
-                p2 = partial.view(sg, 2 * c)
-                pend.add(p2[:, :c], ds, dw, owners=[(ctx.params[0], dw)])
-                pend.add(p2[:, c:], db, owners=[(ctx.params[1], db)])
-                return None, None, dw, db, None
-            waiting = pend.take()
-            if waiting:
-                abi.coeff_bwd_saved(dpc, A, Bm, partial, None, None, b, h, stream)
-                p2 = partial.view(sg, 2 * c)
-                abi.colsum_multi([(p2[:, :c], ds, dw), (p2[:, c:], db)] + waiting, stream)
-            else:
-                abi.coeff_bwd_saved(dpc, A, Bm, partial, ds, db, b, h, stream, dw_dense=dw)
-            return None, None, dw, db, None
-        groups = abi.coeff_bwd_groups(b, h)
-        partial = torch.empty((groups, 2, c), dtype=torch.float32, device=cj.device)
-        if (pend is not None and pend.stack_armed and not pend.stack_done and PendingSums.untouched(*ctx.params)):
-            # the layer stack's backward comes after this node: its first launch carries this node's kernel in trailing
-            # workgroups (feta_ffn_bwd_coeff), its reduction launch the sums
-            pend.coeff_bwd_req = (cj, n_real, s, gb, dpooled.contiguous(), partial, b, n, h)
-            p2 = partial.view(groups, 2 * c)
-            pend.add(p2[:, :c], ds, dw, owners=[(ctx.params[0], dw)])
-            pend.add(p2[:, c:], db, owners=[(ctx.params[1], db)])
-            return None, None, dw, db, None
-        waiting = pend.take() if pend is not None else []
-        if waiting:
-            # ONE reduction launch for this node's partials and every column sum the nodes before it left pending
-            abi.coeff_bwd(cj, n_real, s, gb, dpooled.contiguous(), partial, None, None, b, n, h, stream)
-            p2 = partial.view(groups, 2 * c)
-            abi.colsum_multi([(p2[:, :c], ds, dw), (p2[:, c:], db)] + waiting, stream)
-        else:
-            abi.coeff_bwd(cj, n_real, s, gb, dpooled.contiguous(), partial, ds, db, b, n, h, stream, dw_dense=dw)
-        return None, None, dw, db, None
-
+        dw, db = _coeff_backward(abi, stream, cj, n_real, s, gb, ctx.dims, dpooled)
+        return None, None, dw, db
 
 class DenseLinearFn(torch.autograd.Function):
     """y = x W^T + b for the C x C ``self.linear`` of the coefficient generator
@@ -223,6 +212,37 @@ def dense_linear(x, w, bias):
     return DenseLinearFn.apply(x, w, bias)
 
 
+def _filter_forward(abi, stream, xs, g0, g1, cw, bias, n_real, mode, order, share, batch_first, cat=None):
+    """The dynamic filter's forward launch -> y (token layout of xs).  cat: the further arguments of
+    feta_spec_filter_cat_fwd - linear_cat rides in the launch (out = [xn | y] W_cat^T + b)."""
+    b, n, h, dh = xs.shape
+    y = _new_token(b, n, h, dh, batch_first, xs)
+    if cat is not None:
+        abi.spec_filter_cat_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream, **cat)
+    elif mode == 'cheb':
+        abi.cheb_filter_fwd(xs, g0, cw, bias, n_real, y, order, share, stream)
+    else:
+        abi.spec_filter_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream)
+    return y
+
+
+def _filter_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, mode, order, share, batch_first, cat=None, y=None):
+    """The dynamic filter's backward launch -> (dx, dcoeff, per-block partials of the bias gradient).  cat: the further
+    arguments of feta_spec_filter_cat_bwd - linear_cat's backward rides in the launch, which then starts from cat['dout']
+    instead of dys and needs the filter's output y."""
+    b, n, h, dh = xs.shape
+    dx = _new_token(b, n, h, dh, batch_first, xs)
+    dcoeff = torch.empty_like(coeff)
+    dbp = torch.empty((b * h, dh), dtype=torch.float32, device=xs.device)
+    if cat is not None:
+        abi.spec_filter_cat_bwd(xs, g0, g1, coeff, n_real, y, dx, dcoeff, dbp, order, share, stream, **cat)
+    elif mode == 'cheb':
+        abi.cheb_filter_bwd(xs, g0, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
+    else:
+        abi.spec_filter_bwd(xs, g0, g1, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
+    return dx, dcoeff, dbp
+
+
 class _FilterFn(torch.autograd.Function):
     """x [B,N,H,dh] view, coeff [H*B, P*dh*dh], bias [dh] -> y (same token layout as x),
     zero on padded rows.  mode 'cheb': graph = lhat [B,N,N]; mode 'spec': graph = (u, lam)."""
@@ -230,14 +250,9 @@ class _FilterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, coeff, bias, n_real, g0, g1, mode, order, share, batch_first):
         abi, stream = _lib.backend(x, coeff)
-        b, n, h, dh = x.shape
         xs = _dense_like(x, batch_first)
         coeff = coeff.contiguous()
-        y = _new_token(b, n, h, dh, batch_first, x)
-        if mode == 'cheb':
-            abi.cheb_filter_fwd(xs, g0, coeff, bias, n_real, y, order, share, stream)
-        else:
-            abi.spec_filter_fwd(xs, g0, g1, coeff, bias, n_real, y, order, share, stream)
+        y = _filter_forward(abi, stream, xs, g0, g1, coeff, bias, n_real, mode, order, share, batch_first)
         ctx.save_for_backward(xs, coeff, n_real, g0, g1)
         ctx.cfg = (mode, order, share, batch_first, bias is not None)
         return y
@@ -247,18 +262,11 @@ class _FilterFn(torch.autograd.Function):
         xs, coeff, n_real, g0, g1 = ctx.saved_tensors
         mode, order, share, batch_first, has_bias = ctx.cfg
         abi, stream = _lib.backend(xs)
-        b, n, h, dh = xs.shape
         dys = _dense_like(dy.to(xs.dtype), batch_first)
-        dx = _new_token(b, n, h, dh, batch_first, xs)
-        dcoeff = torch.empty_like(coeff)
-        dbp = torch.empty((b * h, dh), dtype=torch.float32, device=xs.device)
-        if mode == 'cheb':
-            abi.cheb_filter_bwd(xs, g0, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
-        else:
-            abi.spec_filter_bwd(xs, g0, g1, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
+        dx, dcoeff, dbp = _filter_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, mode, order, share, batch_first)
         dbias = None
         if has_bias:
-            dbias = torch.empty(dh, dtype=torch.float32, device=xs.device)
+            dbias = torch.empty(xs.shape[3], dtype=torch.float32, device=xs.device)
             abi.colsum(dbp, dbias, stream)
         return dx, dcoeff, dbias, None, None, None, None, None, None, None
 
@@ -310,19 +318,23 @@ def lin_dw_role_mode():
         return 1
 
 
+def _owners(*pairs):
+    """[(parameter, the gradient tensor its node returns)] without the absent ones, as second tensor objects on the same
+    storage (autograd keeps a returned gradient without copying it only if nobody else holds that tensor object)"""
+    return [(p, g.detach()) for p, g in pairs if p is not None and g is not None]
+
+
 class PendingSums:
-    """Column sums (split-K partial buffer -> gradient) that one backward node of the filter stage leaves for a LATER
-    node of the same backward pass which has a launch to carry them (trailing workgroups of feta_lin_bwd, or the
-    reduction launch of the coefficient generator's backward): every launch of a captured step costs ~4.5 us whatever
-    its size.  The encoder creates one per forward; a node that will flush arms it in forward iff autograd is going
-    to run its backward, and only then do the nodes that run BEFORE it in backward defer: linear_cat -> filter
-    (the filter output is linear_cat's operand) -> coefficient generator (pooled is the filter node's operand)."""
+    """What crosses between the filter stage's autograd node (FilterStageFn) and the fused layer stack's node, one object per
+    forward: every launch of a captured step costs ~4.5 us whatever its size, so work of the one rides in idle workgroups
+    of the other's launches.  Forward: the stack computes s = colsum(gcn.weight) and the coefficient generator's forward.
+    Backward: the stage, which runs first, leaves the generator's kernel, dW / db of the C x C linear and its column sums
+    (split-K partial buffer -> gradient) to the stack's launches, iff that backward follows in the same pass (stack_armed)
+    and nothing can read the gradients before it has run (untouched)."""
 
     def __init__(self):
-        self.armed = False         # FilterFromPooledFn will run a backward (it takes what linear_cat leaves)
-        self.coeff_armed = False   # FilterCoefficientsFn will (it takes whatever is left: the stage's last node)
-        self.stack_armed = False   # the fused layer stack will, in the same backward pass (set by the encoder), and
-        self.stack_done = False    # ... has not yet: its one reduction launch takes what the stage's last node leaves
+        self.stack_armed = False   # the fused layer stack runs its backward in the same pass (set by the encoder), and
+        self.stack_done = False    # ... has not yet: its one reduction launch takes what the stage's node leaves
         self.items = []
         self.owners = []
         self._callback_queued = False
@@ -333,22 +345,17 @@ class PendingSums:
         # ... and the coefficient generator's kernels themselves: its forward shares the launch of the last layer's
         # feed-forward half (it needs that layer's attention matrix only), its backward kernel the first launch of the
         # stack's backward.  coeff_fwd_req = gcn bias (set by the encoder); coeff_fwd_out = (cj, pooled) once run;
-        # coeff_bwd_req = the argument tuple of abi.coeff_bwd left by FilterCoefficientsFn.backward
+        # coeff_bwd_req = the argument tuple of abi.coeff_bwd, or an _abi.CoeffSavedReq, left by _coeff_backward
         self.coeff_fwd_req = None
         self.coeff_fwd_out = None
         self.coeff_bwd_req = None
-        # ... and the tanh pass of that backward: coeff_dsum_req = (cj, n_real, s, gcn_bias, b, n, h), left by
-        # FilterCoefficientsFn.forward when its backward will run; coeff_dsum_out = (A, Bm) once the filter stage's forward
-        # launch has taken it (detached tensors only: this object is reachable from the autograd nodes of the stage)
-        self.coeff_dsum_req = None
-        self.coeff_dsum_out = None
         # ... and dW / db of the generator's C x C linear: lin_dw_req = an _abi.LinDwReq (detached tensors only) left by
-        # FilterFromPooledFn.backward for the first layer's attention backward (fused_stack: the stack's last launch) -
+        # the stage's backward for the first layer's attention backward (fused_stack: the stack's last launch) -
         # or, if that backward has no such launch, for the library at the start of the stack's backward
         self.lin_dw_req = None
 
     def lin_dw_wanted(self, abi, b, n, heads, r, k, n_out):
-        """May FilterFromPooledFn.backward leave dW / db of the [n_out, k] linear (r rows) to the stack's backward for b
+        """May the stage's backward leave dW / db of the [n_out, k] linear (r rows) to the stack's backward for b
         graphs of n nodes?  (the stack asks the launch's own predicate again before it carries the request)"""
         mode = lin_dw_role_mode()
         if mode == 0 or not (self.stack_armed and not self.stack_done) or self.lin_dw_req is not None:
@@ -361,7 +368,7 @@ class PendingSums:
 
     def defer_lin_dw(self, req, owners):
         self.lin_dw_req = req
-        self.owners += [(p_, g_.detach()) for p_, g_ in owners if p_ is not None and g_ is not None]
+        self.owners += _owners(*owners)
         self._queue_finish()
 
     def take_lin_dw(self):
@@ -375,19 +382,16 @@ class PendingSums:
             torch.autograd.Variable._execution_engine.queue_callback(self._finish_pass)
             self._callback_queued = True
 
-    def coeff_dsum_role(self, abi, graphs, k_eig):
-        """Called by the forward that launches feta_spec_filter_cat_fwd for `graphs` graphs on k_eig eigenvectors: -> the
-        argument tuple of abi.coeff_dsum (A and Bm allocated here), or None if nobody asked or the blocks do not fit the
-        slots that launch leaves free (a role workgroup walks at most two blocks: the launch is on the forward's chain)."""
-        req, self.coeff_dsum_req = self.coeff_dsum_req, None
-        if req is None:
-            return None
+    def coeff_dsum_role(self, abi, req, graphs, k_eig):
+        """Called by the forward that launches feta_spec_filter_cat_fwd for `graphs` graphs on k_eig eigenvectors, with
+        req = (cj, n_real, s, gcn_bias, b, n, h) of the coefficient generator: -> the argument tuple of abi.coeff_dsum (A
+        and Bm allocated here: the tanh pass of the generator's backward), or None if the blocks do not fit the slots that
+        launch leaves free (a role workgroup walks at most two blocks: the launch is on the forward's chain)."""
         cj, n_real, s, gb, b, n, h = req
         if not abi.spec_cat_fwd_coeff_fits(graphs, n, k_eig, h * b):
             return None
         A = torch.empty((h * b, s.shape[0]), dtype=torch.float32, device=cj.device)
         Bm = torch.empty_like(A)
-        self.coeff_dsum_out = (A, Bm)
         return (cj, n_real, s, gb, A, Bm, b, n, h)
 
     @staticmethod
@@ -413,9 +417,7 @@ class PendingSums:
         # (a second tensor object on the same storage: autograd keeps a returned gradient without copying it only
         # if nobody else holds a reference to that tensor object)
         self.items.append((partial, out.detach(), None if bcast is None else bcast.detach()))
-        for p, g in owners:
-            if p is not None and g is not None:
-                self.owners.append((p, g.detach()))
+        self.owners += _owners(*owners)
         self._queue_finish()
 
     def take(self):
@@ -469,227 +471,131 @@ class PendingSums:
                     p.grad.copy_(g.view_as(p.grad))
 
 
+# linear_cat folded into the launches of the eigenbasis filter (FilterStageFn): forward feta_spec_filter_cat_fwd (ABI 10),
+# backward feta_spec_filter_cat_bwd (ABI 11).  FETA_CAT_FOLD=0 / FETA_CAT_FOLD_BWD=0: off (A/B timing).
 USE_CAT_FOLD = _os.environ.get('FETA_CAT_FOLD', '1') != '0'
-
-
-class CatFold:
-    """linear_cat folded into the launch of the eigenbasis filter (feta_spec_filter_cat_fwd, ABI 10).  The encoder fills
-    in what linear_cat would read - the stack output `y2` ([N, B, d]; with `tail`: the pre-norm rows whose last BatchNorm the
-    consumer finalizes, fused_stack.StackTail), `w`, `bias` - and hands the object to filter_from_pooled; if the filter's
-    forward takes the fused kernel it leaves linear_cat's output in `out`, and row_linear_cat[_bn] then launches nothing
-    in forward.  0: FETA_CAT_FOLD=0 (A/B timing).
-    Backward (feta_spec_filter_cat_bwd, ABI 11; FETA_CAT_FOLD_BWD=0: off): linear_cat's autograd node runs first - it
-    launches nothing either, allocates its outputs (dxn, the BatchNorm-backward sums of the StackTail contract, one partial row
-    per graph for dW_cat) and leaves them with dout in `bwd`; the filter's node, which autograd runs next (its incoming
-    gradient is linear_cat's dx2, a placeholder nobody reads), fills them in its one launch.  Only when the partial rows
-    have a reduction launch to ride in (PendingSums armed) - else linear_cat's own backward kernel runs as before."""
-
-    def __init__(self, y2, w, bias, tail=None):
-        self.y2, self.w, self.bias, self.tail = y2.detach(), w, bias, tail
-        self.out = None
-        self.y = None          # the filter's output (token view), saved by the fused forward for the fused backward
-        self.bwd_ok = False    # the backward fold is possible for this shape
-        self.bwd = None        # linear_cat's backward -> the filter's backward: dict(dout, dxn, partial, gs, prm)
-
-    def defer_backward(self, dy, y2, x2, w, prm, pending, owners_of, has_bias):
-        """Called by linear_cat's backward: -> (dx1, dx2, dW view, db view, gs) with nothing launched, or None if the
-        backward fold does not apply."""
-        if not (self.bwd_ok and USE_CAT_FOLD_BWD and pending is not None and self.bwd is None and self.y is not None):
-            return None
-        m, k1 = y2.shape
-        ki, no = k1 + x2.shape[1], w.shape[0]
-        nb = _lib.backend(y2)[0].spec_cat_bwd_rows(self.y.shape[0])       # one row per graph, or per workgroup of a walked batch
-        dx1, dx2 = torch.empty_like(y2), torch.empty_like(x2)    # dx2: a placeholder (the filter's node ignores it)
-        partial = torch.empty((nb, no * ki + no), dtype=torch.float32, device=y2.device)
-        dwdb = torch.empty(no * ki + no, dtype=torch.float32, device=y2.device)
-        gs = torch.empty((nb, 2, k1), dtype=torch.float32, device=y2.device) if prm is not None else None
-        self.bwd = dict(dout=dy, dxn=dx1, partial=partial, gs=gs, prm=prm)
-        pending.add(partial, dwdb, owners=[(owners_of[0], dwdb[:no * ki].view(no, ki)),
-                                           (owners_of[1], dwdb[no * ki:] if has_bias else None)])
-        return dx1, dx2, dwdb[:no * ki].view(no, ki), (dwdb[no * ki:] if has_bias else None), gs
-
-
 USE_CAT_FOLD_BWD = _os.environ.get('FETA_CAT_FOLD_BWD', '1') != '0'
+
+
+def _lin_forward(abi, stream, pooled, lin_w, lin_b, gemm_bf16):
+    """coeff = pooled W_lin^T + b_lin under the one GEMM policy -> (coeff fp32, how, lp): how = 'own' (csrc/lin.hip: one
+    16 x 16 tile per wave straight from L2 - where the products are launch-bound), 'lib16' (library bf16 GEMMs on the bf16
+    copies lp = (pooled, W), which the backward reuses) or 'lib' (the library's fp32 GEMM - where they are compute-bound: C
+    = 1024 at the BASELINE shape is 1 GFLOP each, ~12 us at half the fp32 matrix peak; lin.hip is L2-bound there, 31 us)."""
+    r_, k_, n_ = pooled.shape[0], pooled.shape[1], lin_w.shape[0]
+    if gemm_bf16 and r_ >= LIN_LIB_BF16_MIN_ROWS and pooled.is_cuda:
+        p16, w16 = pooled.to(torch.bfloat16), lin_w.to(torch.bfloat16)
+        coeff = torch.mm(p16, w16.t(), out_dtype=torch.float32)
+        if lin_b is not None:
+            coeff += lin_b
+        return coeff, 'lib16', (p16, w16)
+    if abi.lin_supported(r_, k_, n_) and (r_ * k_ * n_ <= LIN_OWN_GEMM_MAX_MACS or gemm_bf16):
+        coeff = torch.empty((r_, n_), dtype=torch.float32, device=pooled.device)
+        abi.lin_fwd(pooled, lin_w, lin_b, coeff, stream, bf16=gemm_bf16)
+        return coeff, 'own', None
+    with _lib.tuned_gemm():
+        return torch.addmm(lin_b, pooled, lin_w.t()), 'lib', None
+
+
+def _lin_backward(abi, stream, how, gemm_bf16, pooled, lin_w, lp, dcoeff, db_lin, sums, need_dpooled, pass_on=False,
+                  dw_role=None):
+    """Backward of _lin_forward -> (dpooled, dW_lin, column sums still to run); db_lin is written (or requested).
+    sums: [(in, out)] column sums the steps before left.  'own': dpooled, dW_lin, db_lin and every sum in ONE launch.
+    Library: dw_role(dcoeff, db_lin) may leave dW_lin / db_lin to a later launch (-> dW_lin, or None) - only the dX product
+    runs here then; the sums, db_lin among them, run here in one launch unless pass_on hands them to the caller."""
+    if how == 'own':
+        dpooled = torch.empty_like(pooled) if need_dpooled else None
+        dw_lin = torch.empty_like(lin_w)
+        abi.lin_bwd(pooled, lin_w, dcoeff, dpooled, dw_lin, db_lin, stream, pairs=sums, bf16=gemm_bf16)
+        return dpooled, dw_lin, []
+    dw_lin = dw_role(dcoeff, db_lin) if (dw_role is not None and how == 'lib') else None
+    left_dw = dw_lin is not None
+    if not left_dw:
+        sums = sums + [(dcoeff, db_lin)]
+    if sums and not pass_on:
+        abi.colsum_multi(sums, stream)
+        sums = []
+    if how == 'lib16':
+        p16, w16 = lp
+        d16 = dcoeff.to(torch.bfloat16)
+        dpooled = torch.mm(d16, w16, out_dtype=torch.float32)
+        dw_lin = torch.mm(d16.t(), p16, out_dtype=torch.float32)
+    else:
+        with _lib.tuned_gemm():
+            dpooled = dcoeff.mm(lin_w)
+            if not left_dw:
+                dw_lin = dcoeff.t().mm(pooled)
+    return dpooled, dw_lin, sums
+
+
+def _filter_step_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, dcoeff_ext, mode, order, share, batch_first,
+                          cat=None, y=None):
+    """The filter's backward as a step in front of _lin_backward -> (dx, dcoeff fp32, dbias, db_lin, [(in, out)] column
+    sums to run): the filter-bias partials and dcoeff (= the gradient of b_lin) become available together, so ONE reduction
+    launch takes both.  dcoeff_ext: the gradient of a regulariser on the coefficients (transformer/models.py:554-584); dys
+    None (and no cat): only the coefficients were used downstream."""
+    if dys is None and cat is None:
+        dcoeff = dcoeff_ext.contiguous()
+        return None, dcoeff, None, torch.empty(dcoeff.shape[1], dtype=torch.float32, device=xs.device), []
+    dx, dcoeff, dbp = _filter_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, mode, order, share, batch_first, cat, y)
+    if dcoeff.dtype != torch.float32:
+        dcoeff = dcoeff.float()      # the C x C linear's gradients accumulate in fp32
+    if dcoeff_ext is not None:
+        dcoeff += dcoeff_ext
+    dh = xs.shape[3]
+    both = torch.empty(dh + dcoeff.shape[1], dtype=torch.float32, device=xs.device)
+    return dx, dcoeff, both[:dh], both[dh:], [(dbp, both[:dh])]
 
 
 class FilterFromPooledFn(torch.autograd.Function):
     """``self.linear`` of the coefficient generator (transformer/models.py:284) and the dynamic filter
     (transformer/models.py:346-360, transformer/ChebNetDynamic.py:132-189) as ONE autograd node:
-    coeff = pooled W_lin^T + b_lin (rocBLAS), y = filter(x; coeff).  -> (y, coeff [H*B, C]).
-    Same kernels as DenseLinearFn + _FilterFn; what the merge buys is one reduction launch for both bias
-    gradients (colsum of the per-block filter-bias partials and colsum of dcoeff = the gradient of b_lin become
-    available together) instead of two, and no dcoeff hand-over through autograd."""
+    coeff = pooled W_lin^T + b_lin, y = filter(x; coeff).  -> (y, coeff [H*B, C]).  The path of every filter stage that
+    is not the one stage of its forward (FilterStageFn): last_layer_filter=False, the op-by-op bf16 path."""
 
     @staticmethod
-    def forward(ctx, x, pooled, lin_w, lin_b, bias, n_real, g0, g1, mode, order, share, batch_first, pending,
-                gemm_bf16=False, cat=None):
+    def forward(ctx, x, pooled, lin_w, lin_b, bias, n_real, g0, g1, mode, order, share, batch_first, gemm_bf16=False):
         abi, stream = _lib.backend(x, pooled)
-        ctx.gemm_bf16 = bool(gemm_bf16)
-        b, n, h, dh = x.shape
         xs = _dense_like(x, batch_first)
-        # fp32 master precision (also what a regulariser sees)
-        lin_w_in = lin_w      # (the parameter itself: PendingSums.untouched looks at its .grad and hooks)
-        pooled, lin_w = pooled.contiguous(), lin_w.contiguous()
-        r_, k_, n_ = pooled.shape[0], pooled.shape[1], lin_w.shape[0]
-        # csrc/lin.hip (one 16 x 16 tile per wave straight from L2, gradient products and column sums in one launch)
-        # where the products are launch-bound; the library GEMM where they are compute-bound (C = 1024 at the
-        # BASELINE shape: 1 GFLOP each, ~12 us at half the fp32 matrix peak; lin.hip is L2-bound there, 31 us)
-        ctx.lib_bf16 = bool(ctx.gemm_bf16 and r_ >= LIN_LIB_BF16_MIN_ROWS and pooled.is_cuda)
-        ctx.own_gemm = (not ctx.lib_bf16 and abi.lin_supported(r_, k_, n_)
-                        and (r_ * k_ * n_ <= LIN_OWN_GEMM_MAX_MACS or ctx.gemm_bf16))
-        ctx.lp = None
-        if ctx.own_gemm:
-            coeff = torch.empty((pooled.shape[0], lin_w.shape[0]), dtype=torch.float32, device=pooled.device)
-            abi.lin_fwd(pooled, lin_w, lin_b, coeff, stream, bf16=ctx.gemm_bf16)
-        elif ctx.lib_bf16:
-            p16, w16 = pooled.to(torch.bfloat16), lin_w.to(torch.bfloat16)
-            coeff = torch.mm(p16, w16.t(), out_dtype=torch.float32)
-            if lin_b is not None:
-                coeff += lin_b
-            ctx.lp = (p16, w16)       # (the backward's operands: no second pair of cast launches)
-        else:
-            with _lib.tuned_gemm():
-                coeff = torch.addmm(lin_b, pooled, lin_w.t())
-        ctx.pending = pending
-        # pooled's gradient flows into FilterCoefficientsFn: if that node flushes, it runs after this one
-        ctx.defer = pending is not None and pending.coeff_armed and ctx.needs_input_grad[1] and not ctx.own_gemm
-        ctx.params = (lin_b, bias)
-        ctx.lin_w_param = lin_w_in
-        if pending is not None and any(ctx.needs_input_grad):
-            pending.armed = True
+        pooled, lin_w = pooled.contiguous(), lin_w.contiguous()      # fp32 master precision (also what a regulariser sees)
+        coeff, how, ctx.lp = _lin_forward(abi, stream, pooled, lin_w, lin_b, bool(gemm_bf16))
         # bf16 storage path: the per-block weights the filter kernel reads are bf16 copies of them
         cw = coeff if x.dtype == torch.float32 else coeff.to(x.dtype)
-        y = _new_token(b, n, h, dh, batch_first, x)
-        fold = (cat is not None and USE_CAT_FOLD and mode == 'spec' and x.dtype == torch.float32 and not batch_first
-                and cat.w.shape == (h * dh, 2 * h * dh) and abi.spec_cat_supported(n, h, dh, order, g0.shape[2], share))
-        if fold:
-            # linear_cat rides in this launch (CatFold): out = [xn | y] W_cat^T + b
-            out = _new_token(b, n, h, dh, batch_first, x)
-            y2v = cat.y2.detach().view(n, b, h, dh).permute(1, 0, 2, 3)
-            kw = {}
-            if cat.tail is not None:
-                t, nm = cat.tail, cat.tail.norm
-                kw = dict(y2_stats=t.st2, Gx=t.G2, gamma=t.gamma, beta=t.beta, bn_out=t.prm2, rmean=nm.running_mean,
-                          rvar=nm.running_var, nbt=nm.num_batches_tracked, momentum=float(nm.momentum), eps=float(nm.eps))
-            # (the coefficient generator's node ran just before this one: if its backward will run and this node's will
-            # too - pooled's gradient comes from here -, the tanh pass of that backward rides in this launch)
-            dsum = (pending.coeff_dsum_role(abi, b, g0.shape[2]) if (pending is not None and ctx.needs_input_grad[1])
-                    else None)
-            abi.spec_filter_cat_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream, y2=y2v, w_cat=cat.w.detach().contiguous(),
-                                    b_cat=None if cat.bias is None else cat.bias.detach(), out=out, dsum=dsum, **kw)
-            cat.out = out.permute(1, 0, 2, 3).reshape(n * b, h * dh)      # (a view: [N, B, d] rows)
-            cat.y = y.detach()      # (another tensor object: the returned y gets this node as grad_fn - kept in ctx.cat it would be a cycle)
-            cat.bwd_ok = bool(abi.spec_cat_bwd_supported(n, h, dh, order, g0.shape[2], share))
-        elif mode == 'cheb':
-            abi.cheb_filter_fwd(xs, g0, cw, bias, n_real, y, order, share, stream)
-        else:
-            abi.spec_filter_fwd(xs, g0, g1, cw, bias, n_real, y, order, share, stream)
-        if pending is not None:
-            pending.coeff_dsum_req = None     # (not taken: the backward recomputes the tanh, as before)
+        y = _filter_forward(abi, stream, xs, g0, g1, cw, bias, n_real, mode, order, share, batch_first)
         ctx.save_for_backward(xs, cw, pooled, lin_w, n_real, g0, g1)
-        ctx.cfg = (mode, order, share, batch_first, bias is not None)
-        ctx.cat = cat if fold else None
+        ctx.cfg = (mode, order, share, batch_first, bias is not None, how, bool(gemm_bf16))
         ctx.set_materialize_grads(False)
         return y, coeff
 
     @staticmethod
     def backward(ctx, dy, dcoeff_ext):
         xs, coeff, pooled, lin_w, n_real, g0, g1 = ctx.saved_tensors
-        mode, order, share, batch_first, has_bias = ctx.cfg
+        mode, order, share, batch_first, has_bias, how, gemm_bf16 = ctx.cfg
         abi, stream = _lib.backend(xs)
-        b, n, h, dh = xs.shape
-        waiting = ctx.pending.take() if ctx.pending is not None else []
-        sums = []           # (in, out) column sums still to run
-        if dy is None:      # only the coefficients were used downstream
-            dx, dbias = None, None
-            dcoeff = dcoeff_ext.contiguous()
-            db_lin = torch.empty(dcoeff.shape[1], dtype=torch.float32, device=xs.device)
-        else:
-            st = None
-            if ctx.cat is not None and ctx.cat.bwd is not None:
-                st, ctx.cat.bwd = ctx.cat.bwd, None
-            dx = _new_token(b, n, h, dh, batch_first, xs)
-            dcoeff = torch.empty_like(coeff)
-            dbp = torch.empty((b * h, dh), dtype=torch.float32, device=xs.device)
-            if st is not None:
-                # linear_cat's backward rides in this launch (CatFold): dy is its placeholder - the kernel starts from dout
-                cat = ctx.cat
-                tv = lambda t: t.view(n, b, h, dh).permute(1, 0, 2, 3)
-                abi.spec_filter_cat_bwd(xs, g0, g1, coeff, n_real, cat.y, dx, dcoeff, dbp, order, share, stream,
-                                        dout=tv(st['dout']), y2=tv(cat.y2.detach()), w_cat=cat.w.detach().contiguous(),
-                                        dxn=tv(st['dxn']), partial=st['partial'], y2_bn=st['prm'], gs=st['gs'])
-            else:
-                dys = _dense_like(dy.to(xs.dtype), batch_first)
-            if st is not None:
-                pass
-            elif mode == 'cheb':
-                abi.cheb_filter_bwd(xs, g0, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
-            else:
-                abi.spec_filter_bwd(xs, g0, g1, coeff, n_real, dys, dx, dcoeff, dbp, order, share, stream)
-            if dcoeff.dtype != torch.float32:
-                dcoeff = dcoeff.float()      # the C x C linear's gradients accumulate in fp32
-            if dcoeff_ext is not None:   # a regulariser on the coefficients (transformer/models.py:554-584)
-                dcoeff += dcoeff_ext
-            both = torch.empty(dh + dcoeff.shape[1], dtype=torch.float32, device=xs.device)
-            dbias, db_lin = both[:dh], both[dh:]
-            sums.append((dbp, dbias))
-        sums += waiting
-        if ctx.own_gemm:
-            # dpooled, dW_lin, db_lin and every pending column sum in ONE launch (csrc/lin.hip)
-            dpooled = torch.empty_like(pooled) if ctx.needs_input_grad[1] else None
-            dw_lin = torch.empty_like(lin_w)
-            abi.lin_bwd(pooled, lin_w, dcoeff, dpooled, dw_lin, db_lin, stream, pairs=sums, bf16=ctx.gemm_bf16)
-        else:
-            # dW_lin and db_lin as a role of the stack's last launch (PendingSums.lin_dw_req): only the dX product runs here
-            dw_req = None
-            pend = ctx.pending
-            if (pend is not None and not ctx.lib_bf16 and dcoeff.dtype == torch.float32 and pooled.dtype == torch.float32
-                    and lin_w.dtype == torch.float32 and ctx.params[0] is not None
-                    and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
-                    and pend.lin_dw_wanted(abi, b, n, h, dcoeff.shape[0], pooled.shape[1], dcoeff.shape[1])
-                    and PendingSums.untouched(ctx.lin_w_param, ctx.params[0])):
-                dw_lin = torch.empty_like(lin_w)
-                dw_req = LinDwReq(dcoeff, pooled, dw_lin, db_lin)
-                pend.defer_lin_dw(dw_req, [(ctx.lin_w_param, dw_lin), (ctx.params[0], db_lin)])
-            else:
-                sums.append((dcoeff, db_lin))
-            if not sums:
-                pass
-            elif ctx.defer and PendingSums.untouched(*ctx.params):
-                for pr in sums:
-                    ctx.pending.add(*pr)
-                # (dbias is None when only the coefficients were used downstream - a regulariser on them, dy is None)
-                ctx.pending.owners += [(p_, g_.detach()) for p_, g_ in ((ctx.params[0], db_lin), (ctx.params[1], dbias))
-                                       if p_ is not None and g_ is not None]
-            else:
-                abi.colsum_multi(sums, stream)
-            if ctx.lib_bf16:
-                p16, w16 = ctx.lp
-                d16 = dcoeff.to(torch.bfloat16)
-                dpooled = torch.mm(d16, w16, out_dtype=torch.float32)
-                dw_lin = torch.mm(d16.t(), p16, out_dtype=torch.float32)
-            elif dw_req is not None:
-                with _lib.tuned_gemm():
-                    dpooled = dcoeff.mm(lin_w)
-            else:
-                with _lib.tuned_gemm():
-                    dpooled, dw_lin = dcoeff.mm(lin_w), dcoeff.t().mm(pooled)
-        if not has_bias:
-            dbias = None
-        return (dx, dpooled, dw_lin, db_lin, dbias) + (None,) * 10
+        dys = None if dy is None else _dense_like(dy.to(xs.dtype), batch_first)
+        dx, dcoeff, dbias, db_lin, sums = _filter_step_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, dcoeff_ext,
+                                                                mode, order, share, batch_first)
+        dpooled, dw_lin, _ = _lin_backward(abi, stream, how, gemm_bf16, pooled, lin_w, ctx.lp, dcoeff, db_lin, sums,
+                                           ctx.needs_input_grad[1])
+        return (dx, dpooled, dw_lin, db_lin, dbias if has_bias else None) + (None,) * 8
 
 
 def filter_from_pooled(x, pooled, lin_w, lin_b, bias, n_real, graph, mode, order, heads_share_graph=False,
-                       batch_first=False, pending=None, gemm_bf16=False, cat=None):
+                       batch_first=False, gemm_bf16=False):
     """x [B,N,H,dh] view, pooled [H*B, C] -> (y, coeff [H*B, C]); graph = (lhat,) | (u, lam)."""
+    g0, g1 = _graph_operands(graph, mode, x.dtype)
+    return FilterFromPooledFn.apply(x, pooled, lin_w, lin_b, bias, n_real, g0, g1, mode, order,
+                                    bool(heads_share_graph), batch_first, bool(gemm_bf16))
+
+
+def _graph_operands(graph, mode, dtype):
     g0 = graph[0].contiguous()
     g1 = graph[1].contiguous() if len(graph) > 1 else None
-    if x.dtype != torch.float32:
+    if dtype != torch.float32:
         if mode != 'spec':
             raise NotImplementedError("the bf16 storage path runs the eigenbasis filter (filter_mode='spectral')")
-        g0 = g0.to(x.dtype)      # U travels as bf16; lambda and t_k(lambda) stay fp32
-    return FilterFromPooledFn.apply(x, pooled, lin_w, lin_b, bias, n_real, g0, g1, mode, order,
-                                    bool(heads_share_graph), batch_first, pending, bool(gemm_bf16), cat)
+        g0 = g0.to(dtype)      # U travels as bf16; lambda and t_k(lambda) stay fp32
+    return g0, g1
 
 
 class RowLinearFn(torch.autograd.Function):
@@ -741,118 +647,204 @@ class RowLinearFn(torch.autograd.Function):
         return dx, dw, db, None, (dy if has_res else None), None, None, None
 
 
+def _cat_forward(abi, stream, x1, x2, w, bias, tail=None):
+    """y = [x1 | x2] W^T + b on [M, .] rows without materialising the concatenation (linear_cat, transformer/models.py:
+    223-224).  tail (fused_stack.StackTail): x1 is the pre-norm y2 of the fused BatchNorm stack - the launch finalizes the
+    statistics the stack left there (publishing tail.prm2) and normalises inside the operand loads."""
+    m, k1 = x1.shape
+    ki, no = k1 + x2.shape[1], w.shape[0]
+    y = torch.empty((m, no), dtype=torch.float32, device=x1.device)
+    d = abi.rowlin_ex(m, ki, no, x=x1, x2=x2, x_split=k1, w=w, bias=bias, y=y, **_tail_kw(tail, 'x_stats', 'x_'))
+    abi.rowlin_fwd_ex(d, stream)
+    return y
+
+
+def _tail_kw(tail, stats, pre):
+    """the arguments with which a launch finalizes the BatchNorm a StackTail describes, under that launch's names"""
+    if tail is None:
+        return {}
+    nm = tail.norm
+    return {stats: tail.st2, 'Gx': tail.G2, pre + 'gamma': tail.gamma, pre + 'beta': tail.beta, pre + 'bn_out': tail.prm2,
+            pre + 'rmean': nm.running_mean, pre + 'rvar': nm.running_var, pre + 'nbt': nm.num_batches_tracked,
+            'momentum': float(nm.momentum), 'eps': float(nm.eps)}
+
+
+def _cat_backward(abi, stream, x1, x2, w, dy, prm2=None, reduce=True):
+    """Backward of _cat_forward -> (dx1, dx2, dwdb = [dW | db] flat, split-K partial rows, gs).  prm2 (the BatchNorm
+    parameter block of a StackTail): dx1 is the gradient w.r.t. the NORMALISED x1 and gs holds the partial sums its
+    BatchNorm backward needs.  reduce=False: the launch leaves the partial rows for the caller's next reduction launch."""
+    m, k1 = x1.shape
+    ki, no = k1 + x2.shape[1], w.shape[0]
+    dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
+    partial = torch.empty((abi.rowlin_chunks(m), no * ki + no), dtype=torch.float32, device=x1.device)
+    dwdb = torch.empty(no * ki + no, dtype=torch.float32, device=x1.device)
+    gs, kw = None, {}
+    if prm2 is not None:
+        gs = torch.empty((abi.rowlin_blocks(m), 2, k1), dtype=torch.float32, device=x1.device)
+        kw = dict(x_bn=prm2, sum_y=x1, sum_bn=prm2, sum_out=gs)
+    d = abi.rowlin_ex(m, ki, no, x=x1, x2=x2, x_split=k1, w=w, dy=dy, dx=dx1, dx2=dx2, partial=partial,
+                      partial_ld=(0 if reduce else no * ki + no), **kw)
+    abi.rowlin_bwd_ex(d, dwdb if reduce else None, stream)
+    return dx1, dx2, dwdb, partial, gs
+
+
+def _cat_grads(dwdb, w, has_bias):
+    no, ki = w.shape
+    return dwdb[:no * ki].view(no, ki), (dwdb[no * ki:] if has_bias else None)
+
+
 class RowLinearCatFn(torch.autograd.Function):
-    """y = [x1 | x2] W^T + b without materialising the concatenation (linear_cat,
-    transformer/models.py:223-224); backward writes dx1 and dx2 directly."""
+    """linear_cat as a node of its own (_cat_forward / _cat_backward).  With tail, the StackTail contract: backward
+    returns, for x1, the gradient w.r.t. the normalised tensor and leaves the BatchNorm backward partial sums in tail.gs."""
 
     @staticmethod
-    def forward(ctx, x1, x2, w, bias, pending=None, done=None, fold=None):
+    def forward(ctx, x1, x2, w, bias, tail=None):
         abi, stream = _lib.backend(x1, x2, w)
-        ctx.defer = pending if (pending is not None and pending.armed and x2.requires_grad) else None
-        ctx.fold = fold if done is not None else None
-        ctx.params = (w, bias)
         x1, x2, w = x1.contiguous(), x2.contiguous(), w.contiguous()
-        m, k1 = x1.shape
-        ki, no = k1 + x2.shape[1], w.shape[0]
-        if done is not None:     # the filter's launch computed it (CatFold)
-            y = done
-        else:
-            y = torch.empty((m, no), dtype=torch.float32, device=x1.device)
-            d = abi.rowlin_ex(m, ki, no, x=x1, x2=x2, x_split=k1, w=w, bias=bias, y=y)
-            abi.rowlin_fwd_ex(d, stream)
-        ctx.save_for_backward(x1, x2, w)
-        ctx.has_bias = bias is not None
+        y = _cat_forward(abi, stream, x1, x2, w, bias, tail)
+        ctx.save_for_backward(x1, x2, w, None if tail is None else tail.prm2)
+        ctx.tail, ctx.has_bias = tail, bias is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x1, x2, w = ctx.saved_tensors
+        x1, x2, w, prm2 = ctx.saved_tensors
         abi, stream = _lib.backend(x1)
-        m, k1 = x1.shape
-        ki, no = k1 + x2.shape[1], w.shape[0]
-        dy = dy.contiguous()
-        if ctx.defer is not None and not PendingSums.untouched(*ctx.params):
-            ctx.defer = None
-        if ctx.fold is not None and ctx.defer is not None:
-            r = ctx.fold.defer_backward(dy, x1, x2, w, None, ctx.defer, ctx.params, ctx.has_bias)
-            if r is not None:
-                return r[0], r[1], r[2], r[3], None, None, None
-        dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
-        partial = torch.empty((abi.rowlin_chunks(m), no * ki + no), dtype=torch.float32, device=x1.device)
-        dwdb = torch.empty(no * ki + no, dtype=torch.float32, device=x1.device)
-        d = abi.rowlin_ex(m, ki, no, x=x1, x2=x2, x_split=k1, w=w, dy=dy, dx=dx1, dx2=dx2, partial=partial,
-                          partial_ld=(no * ki + no if ctx.defer is not None else 0))
-        if ctx.defer is not None:     # the filter's backward reduces the partials inside its own launch
-            abi.rowlin_bwd_ex(d, None, stream)
-            ctx.defer.add(partial, dwdb, owners=[(ctx.params[0], dwdb[:no * ki].view(no, ki)),
-                                                 (ctx.params[1], dwdb[no * ki:] if ctx.has_bias else None)])
-        else:
-            abi.rowlin_bwd_ex(d, dwdb, stream)
-        return dx1, dx2, dwdb[:no * ki].view(no, ki), (dwdb[no * ki:] if ctx.has_bias else None), None, None, None
+        dx1, dx2, dwdb, _, gs = _cat_backward(abi, stream, x1, x2, w, dy.contiguous(), prm2)
+        if ctx.tail is not None:
+            ctx.tail.gs = gs
+        return (dx1, dx2) + _cat_grads(dwdb, w, ctx.has_bias) + (None,)
 
 
-class RowLinearCatBNFn(torch.autograd.Function):
-    """linear_cat (transformer/models.py:223-224) over [BN(y2) | x2] where BN is the last BatchNorm of the fused
-    layer stack, never materialised: forward finalizes the statistics the stack left in `tail` and normalises inside
-    the operand loads; backward returns, for y2, the gradient w.r.t. the NORMALISED tensor and leaves the BatchNorm
-    backward partial sums in tail.gs (fused_stack.StackTail contract)."""
+class FilterStageFn(torch.autograd.Function):
+    """The ONE filter stage of a forward as one autograd node: coefficient generator -> C x C linear -> dynamic filter ->
+    linear_cat, each step the function the plain ops run.  (y2 [N,B,d] stack output - with tail the pre-norm rows -, x
+    [B,N,H,dh] per-head rows, the seven parameters | attn, n_real, graph operands, tail, pending, cfg) -> (out [N,B,.],
+    coeff [H*B, C]).  cfg = (mode, order, share, gemm_bf16, cat, grad mode): cat None - the node ends at the filter (out = the
+    filtered rows, y2 unused); 'rows' - linear_cat inside; 'fold' - and riding in the filter's launches where they take it.
+    Backward runs linear_cat, the filter, the linear and the generator in program order; a column sum that a later step's
+    launch carries travels in a local list, and what the stack's launches carry leaves through pending (PendingSums)."""
 
     @staticmethod
-    def forward(ctx, y2, x2, w, bias, tail, pending=None, done=None, fold=None):
-        abi, stream = _lib.backend(y2, x2, w)
-        ctx.defer = pending if (pending is not None and pending.armed and x2.requires_grad) else None
-        ctx.fold = fold if done is not None else None
-        ctx.params = (w, bias)
-        y2, x2, w = y2.contiguous(), x2.contiguous(), w.contiguous()
-        m, k1 = y2.shape
-        ki, no = k1 + x2.shape[1], w.shape[0]
-        if done is not None:     # the filter's launch computed it and finalized the BatchNorm (CatFold: tail.prm2 is published)
-            out = done
+    def forward(ctx, y2, x, gcn_w, gcn_b, lin_w, lin_b, bias, cat_w, cat_b, attn, n_real, g0, g1, tail, pending, cfg):
+        mode, order, share, gemm_bf16, cat, grad_mode = cfg
+        abi, stream = _lib.backend(x, attn)
+        ctx.set_materialize_grads(False)
+        need = [grad_mode and g for g in ctx.needs_input_grad]     # (set for a parameter also where no graph is recorded)
+        coeff_live = need[2] or need[3]                                    # the generator's backward will have work
+        filt_live = coeff_live or need[1] or need[4] or need[5] or need[6]     # ... the filter's and the linear's
+        b, n, h, dh = x.shape
+        d = h * dh
+        tok = lambda t: t.view(n, b, h, dh).permute(1, 0, 2, 3)     # [N*B, d] rows -> token view
+        rows = lambda t: t.permute(1, 0, 2, 3).reshape(n * b, d)    # ... and back (a view)
+        pooled, cj, s, gb = _coeff_forward(abi, stream, attn, n_real, gcn_w, gcn_b, pending)
+        xs = _dense_like(x, False)
+        lw = lin_w.contiguous()
+        coeff, how, ctx.lp = _lin_forward(abi, stream, pooled, lw, lin_b, gemm_bf16)
+        y2r = cw = A = Bm = dsum = None
+        if cat is not None:
+            y2r, cw = y2.reshape(n * b, d).contiguous(), cat_w.contiguous()
+        fold = (cat == 'fold' and USE_CAT_FOLD and mode == 'spec' and cat_w.shape == (d, 2 * d)
+                and bool(abi.spec_cat_supported(n, h, dh, order, g0.shape[2], share)))
+        if fold:
+            if USE_COEFF_DSUM and coeff_live and n <= 64 and h == 4 and h * b <= COEFF_ROLE_MAX_BLOCKS:
+                # the generator's backward will run: this launch, which leaves most of the chip idle, may compute the tanh
+                # part of it (A, Bm: feta_coeff_dsum).  4 heads only: feta_spec_filter_cat_fwd_coeff has no 8-head form
+                dsum = pending.coeff_dsum_role(abi, (cj, n_real, s, gb, b, n, h), b, g0.shape[2])
+                if dsum is not None:
+                    A, Bm = dsum[4], dsum[5]
+            out = _new_token(b, n, h, dh, False, x)
+            y = _filter_forward(abi, stream, xs, g0, g1, coeff, bias, n_real, mode, order, share, False,
+                                cat=dict(y2=tok(y2r), w_cat=cw, b_cat=cat_b, out=out, dsum=dsum,
+                                         **_tail_kw(tail, 'y2_stats', '')))
+            out = rows(out)
         else:
-            out = torch.empty((m, no), dtype=torch.float32, device=y2.device)
-            nm = tail.norm
-            d = abi.rowlin_ex(m, ki, no, x=y2, x2=x2, x_split=k1, w=w, bias=bias, y=out, x_stats=tail.st2, Gx=tail.G2,
-                              x_gamma=tail.gamma, x_beta=tail.beta, x_bn_out=tail.prm2, x_rmean=nm.running_mean,
-                              x_rvar=nm.running_var, x_nbt=nm.num_batches_tracked, momentum=float(nm.momentum),
-                              eps=float(nm.eps))
-            abi.rowlin_fwd_ex(d, stream)
-        ctx.save_for_backward(y2, x2, w, tail.prm2)
-        ctx.tail = tail
-        ctx.has_bias = bias is not None
-        return out
+            y = _filter_forward(abi, stream, xs, g0, g1, coeff, bias, n_real, mode, order, share, False)
+            out = rows(y) if cat is None else _cat_forward(abi, stream, y2r, rows(y), cw, cat_b, tail)
+        ctx.save_for_backward(xs, coeff, pooled, lw, n_real, g0, g1, cj, s, gb, y2r, cw, None if tail is None else tail.prm2,
+                              y if cat is not None else None, A, Bm)
+        fold_bwd = fold and bool(abi.spec_cat_bwd_supported(n, h, dh, order, g0.shape[2], share))
+        ctx.cfg = (mode, order, share, gemm_bf16, cat, how, fold_bwd, coeff_live, filt_live)
+        ctx.dims = (b, n, h, gcn_w.shape[0])
+        ctx.params = (gcn_w, gcn_b, lin_w, lin_b, bias, cat_w, cat_b)     # (the parameters themselves: untouched())
+        ctx.tail, ctx.pending = tail, pending
+        return out.view(n, b, -1), coeff
 
     @staticmethod
-    def backward(ctx, dy):
-        y2, x2, w, prm2 = ctx.saved_tensors
-        abi, stream = _lib.backend(y2)
-        m, k1 = y2.shape
-        ki, no = k1 + x2.shape[1], w.shape[0]
-        dy = dy.contiguous()
-        if ctx.defer is not None and not PendingSums.untouched(*ctx.params):
-            ctx.defer = None
-        if ctx.fold is not None and ctx.defer is not None:
-            r = ctx.fold.defer_backward(dy, y2, x2, w, prm2, ctx.defer, ctx.params, ctx.has_bias)
-            if r is not None:
-                ctx.tail.gs = r[4]      # (one row per graph, filled by the filter's launch: the stack's node runs behind it)
-                return r[0], r[1], r[2], r[3], None, None, None, None
-        dx1, dx2 = torch.empty_like(y2), torch.empty_like(x2)
-        partial = torch.empty((abi.rowlin_chunks(m), no * ki + no), dtype=torch.float32, device=y2.device)
-        dwdb = torch.empty(no * ki + no, dtype=torch.float32, device=y2.device)
-        gs = torch.empty((abi.rowlin_blocks(m), 2, k1), dtype=torch.float32, device=y2.device)
-        d = abi.rowlin_ex(m, ki, no, x=y2, x_bn=prm2, x2=x2, x_split=k1, w=w, dy=dy, dx=dx1, dx2=dx2, partial=partial,
-                          partial_ld=(no * ki + no if ctx.defer is not None else 0), sum_y=y2, sum_bn=prm2, sum_out=gs)
-        if ctx.defer is not None:     # the filter's backward reduces the partials inside its own launch
-            abi.rowlin_bwd_ex(d, None, stream)
-            ctx.defer.add(partial, dwdb, owners=[(ctx.params[0], dwdb[:no * ki].view(no, ki)),
-                                                 (ctx.params[1], dwdb[no * ki:] if ctx.has_bias else None)])
-        else:
-            abi.rowlin_bwd_ex(d, dwdb, stream)
-        ctx.tail.gs = gs
-        return dx1, dx2, dwdb[:no * ki].view(no, ki), (dwdb[no * ki:] if ctx.has_bias else None), None, None, None, None
+    def backward(ctx, dout, dcoeff_ext):
+        if dout is None and dcoeff_ext is None:
+            return (None,) * 16
+        xs, coeff, pooled, lw, n_real, g0, g1, cj, s, gb, y2r, cw, prm2, y, A, Bm = ctx.saved_tensors
+        mode, order, share, gemm_bf16, cat, how, fold_bwd, coeff_live, filt_live = ctx.cfg
+        gcn_w, gcn_b, lin_w, lin_b, bias, cat_w, cat_b = ctx.params
+        pend, need = ctx.pending, ctx.needs_input_grad
+        abi, stream = _lib.backend(xs)
+        b, n, h, dh = xs.shape
+        tok = lambda t: t.view(n, b, h, dh).permute(1, 0, 2, 3)
+        sums, owners = [], []     # column sums that a later launch of this backward carries, and the gradients they complete
+        dy2 = dx = dgw = dgb = dlw = dlb = dfb = dcw = dcb = dys = fold = dpooled = None
+        # -- linear_cat, or its fold into the filter's launch
+        if dout is not None and cat is None:
+            dys = tok(dout.to(xs.dtype).contiguous())
+        elif dout is not None:
+            dyr = dout.reshape(n * b, -1).contiguous()
+            # (the same launches as while linear_cat was a node of its own, whose gradients somebody could read before the
+            # filter's launch had reduced them: its partial rows ride along only where that held)
+            ride = filt_live and PendingSums.untouched(cat_w, cat_b)
+            if fold_bwd and ride and USE_CAT_FOLD_BWD:
+                # nothing is launched here: the filter's launch starts from dout and writes dy2, gs and the partial rows
+                no, ki = cw.shape
+                nb = abi.spec_cat_bwd_rows(b)
+                dy2 = torch.empty_like(y2r)
+                partial = torch.empty((nb, no * ki + no), dtype=torch.float32, device=xs.device)
+                dwdb = torch.empty(no * ki + no, dtype=torch.float32, device=xs.device)
+                gs = torch.empty((nb, 2, y2r.shape[1]), dtype=torch.float32, device=xs.device) if prm2 is not None else None
+                fold = dict(dout=tok(dyr), y2=tok(y2r), w_cat=cw, dxn=tok(dy2), partial=partial, y2_bn=prm2, gs=gs)
+            else:
+                dy2, dx2, dwdb, partial, gs = _cat_backward(abi, stream, y2r, y.permute(1, 0, 2, 3).reshape(n * b, h * dh),
+                                                            cw, dyr, prm2, reduce=not ride)
+                dys = tok(dx2)
+            dcw, dcb = _cat_grads(dwdb, cw, cat_b is not None)
+            if ride:
+                sums.append((partial, dwdb))
+                owners += _owners((cat_w, dcw), (cat_b, dcb))
+            if ctx.tail is not None:
+                ctx.tail.gs = gs      # (StackTail contract: the stack's node runs behind this one)
+        # -- the filter and the C x C linear
+        if filt_live:
+            dx, dcoeff, dfb, dlb, own = _filter_step_backward(abi, stream, xs, g0, g1, coeff, n_real, dys, dcoeff_ext, mode,
+                                                              order, share, False, fold, y)
+
+            def dw_role(dcoeff, db_lin):
+                # dW_lin and db_lin as a role of the stack's last launch (PendingSums.lin_dw_req)
+                if not (need[4] and need[5]
+                        and pend.lin_dw_wanted(abi, b, n, h, dcoeff.shape[0], pooled.shape[1], dcoeff.shape[1])
+                        and PendingSums.untouched(lin_w, lin_b)):
+                    return None
+                dw_lin = torch.empty_like(lw)
+                pend.defer_lin_dw(LinDwReq(dcoeff, pooled, dw_lin, db_lin), [(lin_w, dw_lin), (lin_b, db_lin)])
+                return dw_lin
+            # (library GEMMs: the sums wait for the generator's reduction launch - where they did as a node's, see above)
+            pass_on = coeff_live and how != 'own' and PendingSums.untouched(lin_b, bias)
+            dpooled, dlw, sums = _lin_backward(abi, stream, how, gemm_bf16, pooled, lw, ctx.lp, dcoeff, dlb, own + sums,
+                                               coeff_live, pass_on, dw_role)
+            if sums:
+                owners += _owners((lin_b, dlb), (bias, dfb))
+        # -- the coefficient generator: its reduction launch, or the stack's, takes what is left
+        if coeff_live and dpooled is not None:
+            dgw, dgb = _coeff_backward(abi, stream, cj, n_real, s, gb, ctx.dims, dpooled, None if A is None else (A, Bm),
+                                       pend, (gcn_w, gcn_b), sums, owners)
+        return (None if dy2 is None else dy2.view(n, b, -1), dx, dgw, dgb, dlw, dlb, None if bias is None else dfb, dcw,
+                dcb) + (None,) * 7
 
 
-def row_linear_cat_bn(y2, x2, w, bias, tail, pending=None, done=None, fold=None):
-    return RowLinearCatBNFn.apply(y2, x2, w, bias, tail, pending, done, fold)
+def filter_stage(y2, x, gcn_w, gcn_b, lin_w, lin_b, bias, cat_w, cat_b, attn, n_real, graph, mode, order,
+                 heads_share_graph=False, gemm_bf16=False, cat='fold', tail=None, pending=None):
+    """-> (out [N,B,.], coeff [H*B, C]) of FilterStageFn; graph = (lhat,) | (u, lam); pending: the layer stack's PendingSums"""
+    g0, g1 = _graph_operands(graph, mode, x.dtype)
+    return FilterStageFn.apply(y2, x, gcn_w, gcn_b, lin_w, lin_b, bias, cat_w, cat_b, attn, n_real, g0, g1, tail,
+                               PendingSums() if pending is None else pending,
+                               (mode, order, bool(heads_share_graph), bool(gemm_bf16), cat, torch.is_grad_enabled()))
 
 
 class BatchNormTrainFn(torch.autograd.Function):
@@ -901,9 +893,13 @@ def row_linear(x, w, bias=None, rowscale=None, residual=None, relu=False, want_s
     return RowLinearFn.apply(x, w, bias, rowscale, residual, relu, want_stats, stats_shift)
 
 
-def row_linear_cat(x1, x2, w, bias=None, pending=None, done=None, fold=None):
-    """[x1 | x2] W^T + b on [M, .] rows; needs x1.shape[1] % 16 == 0 and supported total dims."""
-    return RowLinearCatFn.apply(x1, x2, w, bias, pending, done, fold)
+def row_linear_cat(x1, x2, w, bias=None, tail=None):
+    """[x1 | x2] W^T + b on [M, .] rows; needs x1.shape[1] % 16 == 0 and supported total dims.  tail: [BN(x1) | x2], where
+    BN is the last BatchNorm of the fused layer stack, never materialised (row_linear_cat_bn(y2, x2, w, bias, tail))."""
+    return RowLinearCatFn.apply(x1, x2, w, bias, tail)
+
+
+row_linear_cat_bn = row_linear_cat
 
 
 def batch_norm_train(y, stats, gamma, beta, running_mean, running_var, momentum, eps, num_batches_tracked=None):
@@ -1058,8 +1054,8 @@ def attention_core(qkv, pe, n_real, num_heads, need_attn=True, tie_qk=False, bat
     return AttentionCoreFn.apply(qkv, pe, n_real, num_heads, need_attn, tie_qk, batch_first, drop, stab == 'clamp5')
 
 
-def filter_coefficients(attn, n_real, gcn_weight, gcn_bias, pending=None):
-    return FilterCoefficientsFn.apply(attn, n_real, gcn_weight, gcn_bias, pending)
+def filter_coefficients(attn, n_real, gcn_weight, gcn_bias):
+    return FilterCoefficientsFn.apply(attn, n_real, gcn_weight, gcn_bias)
 
 
 def cheb_filter(x, lhat, coeff, bias, n_real, order, heads_share_graph=False, batch_first=False):

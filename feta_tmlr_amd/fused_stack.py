@@ -211,7 +211,7 @@ class StackTail:
     """Hand-over between the BatchNorm stack and the ONE consumer of its output when that consumer is linear_cat
     (transformer/models.py:223-224): the last BatchNorm is then never materialised either.  The stack returns the
     pre-norm y2 of the last layer and leaves its statistics here; linear_cat's forward kernel finalizes them and
-    applies the normalisation inside its operand loads (functional.RowLinearCatBNFn), its backward kernel emits the
+    applies the normalisation inside its operand loads (functional._cat_forward), its backward kernel emits the
     partial sums (sum dout, sum dout * xhat) the BatchNorm backward needs from its dX epilogue.  Contract: the
     gradient that reaches the stack's first output is the gradient w.r.t. the NORMALISED tensor, with `gs` set.
     Saves the bn_apply_fwd and bn_bwd_reduce launches of a step."""
@@ -599,7 +599,7 @@ class FusedEncoderStackFn(torch.autograd.Function):
         if ctx.tail is not None:
             # (StackTail contract) d_final is the gradient w.r.t. BN2(y2); its partial sums came with it
             gs = ctx.tail.gs
-            Gs_cur = G if gs is None else gs.shape[0]     # (row blocks of linear_cat's backward, or one row per graph: CatFold)
+            Gs_cur = G if gs is None else gs.shape[0]     # (row blocks of linear_cat's backward, or one row per graph: the fold into the filter's launch)
             ctx.tail.gs = None
             if gs is None:
                 raise RuntimeError('fused stack: the consumer of the un-normalised output did not leave the '
@@ -884,7 +884,7 @@ def _ln_one_launch_forward(ctx, g, x_pre, layers, need_attn, pending, params):
     y2 - in the layouts and storage type of feta_attn_block_fwd / feta_ffn_fwd.  The saved tensors are views of one
     [L, ...] allocation per kind; x0 of layer l > 0 is y2 of layer l - 1.  The pending forward column sums ride in trailing
     workgroups of the launch; the coefficient generator's forward does not (it reads the attention matrix this launch
-    writes): pending.coeff_fwd_req stays and FilterCoefficientsFn.forward runs its own launch."""
+    writes): pending.coeff_fwd_req stays and the filter stage (functional._coeff_forward) runs its own launch."""
     new, newt = g.new, g.newt
     n, b, d, m, nl, heads, dh, lowp = g.n, g.b, g.d, g.m, g.nl, g.heads, g.dh, g.lowp
     ff = params[6].shape[0]

@@ -120,24 +120,34 @@ class DiffTransformerEncoderGenGCN(nn.Module):
         coeff = FF.dense_linear(pooled, self.linear.weight, self.linear.bias)    # :284
         return coeff.reshape(self.num_heads, attn_weights.shape[0], -1)          # :285
 
-    def _coefficients_and_filter(self, attn_weights, out_each_head, cache, pending=None, cat=None):
+    def _graph_operands(self, cache):
+        if self.filter_mode == 'cheb':
+            return (cache.lhat,), 'cheb'
+        if cache.u is None:
+            raise ValueError("filter_mode='spectral' needs graph_cache.u / graph_cache.lam (collate(..., k_eig=K))")
+        return (cache.u, cache.lam), 'spec'
+
+    def _coefficients_and_filter(self, attn_weights, out_each_head, cache):
         """get_filter_coefficients + filter of one layer (:173, :186-202) with ``self.linear`` folded into the
         filter's autograd node (functional.FilterFromPooledFn).  -> (coeff [H,B,C], out_filtered [N,B,d])"""
         bsz, n, h, dh = out_each_head.shape
-        pooled = FF.filter_coefficients(attn_weights.detach().float(), cache.n_real, self.gcn.weight, self.gcn.bias,
-                                        pending)
-        if self.filter_mode == 'cheb':
-            graph, mode = (cache.lhat,), 'cheb'
-        else:
-            if cache.u is None:
-                raise ValueError("filter_mode='spectral' needs graph_cache.u / graph_cache.lam "
-                                 '(collate(..., k_eig=K))')
-            graph, mode = (cache.u, cache.lam), 'spec'
+        pooled = FF.filter_coefficients(attn_weights.detach().float(), cache.n_real, self.gcn.weight, self.gcn.bias)
+        graph, mode = self._graph_operands(cache)
         y, coeff = FF.filter_from_pooled(out_each_head, pooled, self.linear.weight, self.linear.bias,
                                          self.spectral_gnns.bias, cache.n_real, graph, mode, self.order,
-                                         self.heads_share_graph, pending=pending,
-                                         gemm_bf16=self.storage_dtype != torch.float32, cat=cat)
+                                         self.heads_share_graph, gemm_bf16=self.storage_dtype != torch.float32)
         return coeff.reshape(h, bsz, -1), y.permute(1, 0, 2, 3).reshape(n, bsz, h * dh)
+
+    def _filter_stage(self, output, out_each_head, attn_weights, cache, cat, tail, pending):
+        """The one filter stage of a forward - the two above and linear_cat (:223-224) - as one autograd node
+        (functional.FilterStageFn).  -> (coeff [H,B,C], [N,B,d]: the encoder output, or with cat None out_filtered)"""
+        graph, mode = self._graph_operands(cache)
+        out, coeff = FF.filter_stage(output if cat is not None else None, out_each_head, self.gcn.weight, self.gcn.bias,
+                                     self.linear.weight, self.linear.bias, self.spectral_gnns.bias, self.linear_cat.weight,
+                                     self.linear_cat.bias, attn_weights.detach().float(), cache.n_real, graph, mode,
+                                     self.order, self.heads_share_graph, gemm_bf16=self.storage_dtype != torch.float32,
+                                     cat=cat, tail=tail, pending=pending)
+        return coeff.reshape(self.num_heads, out_each_head.shape[0], -1), out
 
     # -- A3 ---------------------------------------------------------------------------------
     def filter(self, coeff_all_heads, out_each_head, cache):
@@ -147,15 +157,9 @@ class DiffTransformerEncoderGenGCN(nn.Module):
         w = coeff_all_heads.reshape(h * bsz, -1)
         if self.learn_only_filter_order_coeff:
             w = self.spectral_gnns.group_weights(w.reshape(h * bsz, self.order).permute(1, 0))
-        if self.filter_mode == 'cheb':
-            y = FF.cheb_filter(out_each_head, cache.lhat, w, self.spectral_gnns.bias, cache.n_real,
-                               self.order, self.heads_share_graph)
-        else:
-            if cache.u is None:
-                raise ValueError("filter_mode='spectral' needs graph_cache.u / graph_cache.lam "
-                                 '(collate(..., k_eig=K))')
-            y = FF.spec_filter(out_each_head, cache.u, cache.lam, w, self.spectral_gnns.bias,
-                               cache.n_real, self.order, self.heads_share_graph)
+        graph, mode = self._graph_operands(cache)
+        op = FF.cheb_filter if mode == 'cheb' else FF.spec_filter
+        y = op(out_each_head, *graph, w, self.spectral_gnns.bias, cache.n_real, self.order, self.heads_share_graph)
         return y.permute(1, 0, 2, 3).reshape(n, bsz, h * dh)
 
     def _graph_cache(self, graph_cache, edge_index, batch, key_padding_mask, n_pad):
@@ -250,22 +254,25 @@ class DiffTransformerEncoderGenGCN(nn.Module):
             fused = lowp_stack_supported(_lib.backend(output)[0], self.layers, n, src.shape[1], src.shape[-1])
         lowp = lowp and not fused and not infer     # from here on: the op-by-op bf16 path
         # BatchNorm stack whose only consumer is linear_cat: the last BatchNorm is applied inside linear_cat's kernels
-        tail = None
-        if (fused and self.layers[0].batch_norm and self.use_skip_conn and self.norm is None
-                and src.shape[-1] % 16 == 0 and FF.row_linear_supported(2 * src.shape[-1], self.linear_cat.weight.shape[0])):
-            tail = StackTail()
-        # linear_cat's weight-gradient partials are reduced inside the launch of the filter's backward (PendingSums)
-        # (one filter stage per forward only: a parameter that collects several contributions is summed by autograd
-        # as they arrive)
-        pending = FF.PendingSums() if (not lowp and self.last_layer_filter) else None
-        if (pending is not None and fused and not self.learn_only_filter_order_coeff and self.linear.bias is not None):
+        d_model, wc = src.shape[-1], self.linear_cat.weight
+        bn_fused = fused and self.layers[0].batch_norm
+        # linear_cat (:223-224) on the row-linear kernels, without materialising the concatenation
+        cat_rows = self.use_skip_conn and not lowp and d_model % 16 == 0 and FF.row_linear_supported(2 * d_model, wc.shape[0])
+        tail = StackTail() if (bn_fused and cat_rows and self.norm is None) else None
+        # ONE filter stage in the forward, with matrix coefficients: one autograd node (functional.FilterStageFn) which trades
+        # work with the fused stack's launches through `pending` - with linear_cat inside ('rows'), riding in the filter's own
+        # launches where its operands are theirs ('fold')
+        stage = not lowp and self.last_layer_filter and not self.learn_only_filter_order_coeff and self.linear.bias is not None
+        fold = self.norm is None and wc.shape[0] == d_model and (tail is not None or not bn_fused)
+        stage_cat = ('fold' if fold else 'rows') if (stage and cat_rows) else None
+        pending = FF.PendingSums() if stage else None
+        if stage and fused:
             # s = colsum(gcn.weight) of the coefficient generator: computed by trailing workgroups of the stack's
             # first launch instead of a launch of its own
             pending.s = torch.empty(self.gcn.weight.shape[1], dtype=torch.float32, device=src.device)
             pending.fwd_sums = [(self.gcn.weight.detach(), pending.s)]
             # ... and the generator's forward kernel in the launch of the last layer's feed-forward half
             pending.coeff_fwd_req = self.gcn.bias
-        cat = None
         for layer_num, mod in enumerate(self.layers):
             last = layer_num + 1 == self.num_layers
             filt = last or not self.last_layer_filter                            # :169-171
@@ -296,20 +303,18 @@ class DiffTransformerEncoderGenGCN(nn.Module):
                                                   need_weights=filt, degree_rows=degree_rows)
             if not filt:
                 continue
-            if self.learn_only_filter_order_coeff or self.linear.bias is None:
+            if stage:
+                coeff_all_heads, out_filtered = self._filter_stage(output, out_each_head, attn, cache, stage_cat, tail, pending)
+            elif self.learn_only_filter_order_coeff or self.linear.bias is None:
                 coeff_all_heads = self.get_filter_coefficients(attn, masks=src_key_padding_mask,
                                                                n_real=cache.n_real)   # :173
                 out_filtered = self.filter(coeff_all_heads, out_each_head, cache)     # :186-202
             else:
-                # linear_cat (:223-224) can ride in the filter's launch when this is the one filter stage of the forward
-                # and its operands are the row-linear kernels' (functional.CatFold)
-                cat = None
-                if (last and self.last_layer_filter and self.use_skip_conn and not lowp and self.norm is None
-                        and output.dtype == torch.float32 and self.linear_cat.weight.shape[0] == output.shape[-1]
-                        and (tail is not None or not (fused and self.layers[0].batch_norm))):
-                    cat = FF.CatFold(output, self.linear_cat.weight, self.linear_cat.bias, tail)
-                coeff_all_heads, out_filtered = self._coefficients_and_filter(attn, out_each_head, cache, pending, cat)
+                coeff_all_heads, out_filtered = self._coefficients_and_filter(attn, out_each_head, cache)
             coefficients.append(coeff_all_heads)                                  # :198
+            if stage_cat is not None:
+                output = out_filtered     # (linear_cat ran inside the stage's node: the encoder output)
+                continue
             if self.use_skip_conn and allout_filtered is not None:
                 allout_filtered = allout_filtered + out_filtered                  # :209-213
             else:
@@ -318,19 +323,16 @@ class DiffTransformerEncoderGenGCN(nn.Module):
                 output = allout_filtered                                          # :215-216
         if self.use_skip_conn and allout_filtered is not None:
             nn_, bb_, dd_ = output.shape
-            wc = self.linear_cat.weight
-            done = cat.out if (cat is not None and cat.out is not None) else None    # (computed by the filter's launch)
             if lowp:    # plain library bf16 GEMM on bf16 copies of the master weights; the encoder hands back fp32
                 dt = self.storage_dtype
                 output = F.linear(torch.cat((output, allout_filtered.to(dt)), dim=-1), wc.to(dt),
                                   self.linear_cat.bias.to(dt)).float()
             elif tail is not None:
                 output = FF.row_linear_cat_bn(output.reshape(nn_ * bb_, dd_), allout_filtered.reshape(nn_ * bb_, dd_),
-                                              wc, self.linear_cat.bias, tail, pending, done=done, fold=cat).view(nn_, bb_, -1)
-            elif (dd_ % 16 == 0 and FF.row_linear_supported(2 * dd_, wc.shape[0])):
-                # [output | allout_filtered] W^T + b without materialising the concatenation (:223-224)
+                                              wc, self.linear_cat.bias, tail).view(nn_, bb_, -1)
+            elif cat_rows:
                 output = FF.row_linear_cat(output.reshape(nn_ * bb_, dd_), allout_filtered.reshape(nn_ * bb_, dd_),
-                                           wc, self.linear_cat.bias, pending, done=done, fold=cat).view(nn_, bb_, -1)
+                                           wc, self.linear_cat.bias).view(nn_, bb_, -1)
             else:
                 cat = torch.cat((output, allout_filtered), dim=-1)               # :223
                 output, _ = linear_rows(cat.reshape(nn_ * bb_, 2 * dd_), wc, self.linear_cat.bias)   # :224
