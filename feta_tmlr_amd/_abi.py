@@ -377,7 +377,13 @@ class Gather(C.Structure):
     ]
 
 
+class GatherEx(C.Structure):
+    """struct feta_gather_ex (include/feta_hip.h) - field order must match the header."""
+    _fields_ = Gather._fields_ + [('s_lhat', _F), ('lhat', _F), ('lap_sign', _F)]
+
+
 SIGNATURES['feta_batch_gather'] = ([C.POINTER(Gather), _S], C.c_int)
+SIGNATURES['feta_batch_gather_ex'] = ([C.POINTER(GatherEx), _S], C.c_int)
 
 LABELS_NONE, LABELS_GRAPH_F32, LABELS_GRAPH_I64, LABELS_NODE_I64 = 0, 1, 2, 3      # FETA_LABELS_*
 
@@ -1080,10 +1086,23 @@ class Abi:
         """feta_batch_gather: the padded batch of the graphs ids [b] (int32, on the device) out of a store of g graphs.
         Tensor-valued keyword arguments become the descriptor's pointers (store arrays s_*, ids, outputs); an output
         left out is skipped.  dtype: the descriptor's integer (FETA_F32 | FETA_BF16), type of the outputs x and pe."""
-        d = Gather()
+        d = self._gather_desc(Gather, g, b, n, f, k, lap_dim, dtype, label_kind, ptrs)
+        self._check(self.lib.feta_batch_gather(C.byref(d), stream), 'feta_batch_gather')
+
+    @staticmethod
+    def _gather_desc(struct, g, b, n, f, k, lap_dim, dtype, label_kind, ptrs):
+        """a Gather / GatherEx filled from the arguments of batch_gather / batch_gather_ex"""
+        d = struct()
         d.G, d.B, d.N, d.F, d.K, d.lap_dim, d.dtype, d.label_kind = g, b, n, f, k, lap_dim, dtype, label_kind
         _fill(d, ptrs)
-        self._check(self.lib.feta_batch_gather(C.byref(d), stream), 'feta_batch_gather')
+        return d
+
+    def batch_gather_ex(self, g, b, n, stream, f=0, k=0, lap_dim=0, dtype=0, label_kind=LABELS_NONE, **ptrs):
+        """feta_batch_gather_ex: batch_gather with the keyword tensors s_lhat (flat, the geometry and s_pe_off of s_pe),
+        lhat [b, n, n] float32 and lap_sign [lap_dim] float32; without them it writes what batch_gather writes."""
+        _same_dtype(torch.float32, *(ptrs.get(key) for key in ('s_lhat', 'lhat', 'lap_sign')))
+        d = self._gather_desc(GatherEx, g, b, n, f, k, lap_dim, dtype, label_kind, ptrs)
+        self._check(self.lib.feta_batch_gather_ex(C.byref(d), stream), 'feta_batch_gather_ex')
 
 
 def bind(cdll):

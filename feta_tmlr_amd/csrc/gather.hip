@@ -8,17 +8,30 @@
 // column is behind n_real - so nothing is cleared between replays.  A field moves as 16-byte vectors when its width is a
 // multiple of 4 and its pointers are aligned (the entry point decides per field; the store pitches the rows of pe to
 // multiples of 4), element by element otherwise.  No LDS; the only cross-lane step is the prefix sum behind node_off.
+//
+// feta_batch_gather_ex is the same launch with the three additive fields of feta_gather_ex compiled in (EX): the dense
+// scaled Laplacian of filter_mode='cheb' (lhat: the geometry and the block offsets of pe, always fp32) and a sign per
+// column of lap.  feta_batch_gather keeps the kernels without them.
+#include <cstddef>
+#include <cstring>
+
 #include "feta_abi_common.h"
 #include "feta_bf16.h"
 
 namespace feta {
 
 constexpr int kGatherThreads = 256, kGatherRows = 64;
-enum { kGatherVecX = 1, kGatherVecPe = 2, kGatherVecU = 4, kGatherVecLap = 8 };
+enum { kGatherVecX = 1, kGatherVecPe = 2, kGatherVecU = 4, kGatherVecLap = 8, kGatherVecLhat = 16 };
 
 struct GatherArgs {
   feta_gather d;
   int vec;   // kGatherVec* bits: the field's widths and base pointers allow 16-byte loads
+};
+// what feta_gather_ex holds behind its feta_gather
+struct GatherExtra {
+  const float* s_lhat;
+  float* lhat;
+  const float* lap_sign;
 };
 
 __device__ __forceinline__ void gather_st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
@@ -42,29 +55,39 @@ __device__ __forceinline__ int gather_count(const feta_gather& d, int j, int* id
 
 // dst[r, 0..W) for the rows [r0, r1) of one graph: src[r, c] (row pitch `pitch`) where r < n and c < wsrc, else 0.
 // vec: W, pitch and wsrc are multiples of 4 and both sides are aligned for 4-element accesses.
+// colscale [wsrc] or null: a factor per column of the real elements (the padding stays +0).
 template <class T>
 __device__ __forceinline__ void gather_rows(T* dst, int W, int r0, int r1, const float* src, int pitch, int wsrc, int n,
-                                            bool vec) {
+                                            bool vec, const float* colscale = nullptr) {
   if (vec) {
     const int w4 = W >> 2, items = (r1 - r0) * w4;
     for (int it = threadIdx.x; it < items; it += kGatherThreads) {
       const int q = it / w4, r = r0 + q, c = (it - q * w4) << 2;
       float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (r < n && c < wsrc) v = *reinterpret_cast<const float4*>(src + (int64_t)r * pitch + c);
+      if (r < n && c < wsrc) {
+        v = *reinterpret_cast<const float4*>(src + (int64_t)r * pitch + c);
+        if (colscale) {
+          v.x *= colscale[c];
+          v.y *= colscale[c + 1];
+          v.z *= colscale[c + 2];
+          v.w *= colscale[c + 3];
+        }
+      }
       gather_st4(dst + (int64_t)r * W + c, v);
     }
   } else {
     const int items = (r1 - r0) * W;
     for (int it = threadIdx.x; it < items; it += kGatherThreads) {
       const int q = it / W, r = r0 + q, c = it - q * W;
-      const float v = (r < n && c < wsrc) ? src[(int64_t)r * pitch + c] : 0.0f;
+      float v = 0.0f;
+      if (r < n && c < wsrc) v = colscale ? src[(int64_t)r * pitch + c] * colscale[c] : src[(int64_t)r * pitch + c];
       Num<T>::st(dst + (int64_t)r * W + c, v);
     }
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(kGatherThreads) void batch_gather_kernel(GatherArgs a) {
+template <class T, bool EX>
+__device__ __forceinline__ void batch_gather_body(const GatherArgs& a, const GatherExtra& e) {
   const feta_gather& d = a.d;
   const int b = blockIdx.x, N = d.N;
   const int r0 = blockIdx.y * kGatherRows, r1 = min(N, r0 + kGatherRows);
@@ -82,7 +105,13 @@ __global__ __launch_bounds__(kGatherThreads) void batch_gather_kernel(GatherArgs
   }
   if (d.u) gather_rows(d.u + (int64_t)b * N * d.K, d.K, r0, r1, d.s_u + off * d.K, d.K, d.K, n, (a.vec & kGatherVecU) != 0);
   if (d.lap) gather_rows(d.lap + (int64_t)b * N * d.lap_dim, d.lap_dim, r0, r1, d.s_lap + off * d.lap_dim, d.lap_dim,
-                         d.lap_dim, n, (a.vec & kGatherVecLap) != 0);
+                         d.lap_dim, n, (a.vec & kGatherVecLap) != 0, EX ? e.lap_sign : nullptr);
+  if (EX && e.lhat) {
+    const int64_t poff = n > 0 ? d.s_pe_off[id] : 0;
+    const int pitch = (n + 3) & ~3;
+    const bool vec = (a.vec & kGatherVecLhat) != 0 && (poff & 3) == 0;
+    gather_rows(e.lhat + (int64_t)b * N * N, N, r0, r1, e.s_lhat + poff, pitch, vec ? pitch : n, n, vec);
+  }
 
   // one value per node
   for (int i = r0 + threadIdx.x; i < r1; i += kGatherThreads) {
@@ -119,13 +148,18 @@ __global__ __launch_bounds__(kGatherThreads) void batch_gather_kernel(GatherArgs
   }
 }
 
-}  // namespace feta
+template <class T>
+__global__ __launch_bounds__(kGatherThreads) void batch_gather_kernel(GatherArgs a) {
+  batch_gather_body<T, false>(a, GatherExtra{});
+}
 
-using namespace feta;
+template <class T>
+__global__ __launch_bounds__(kGatherThreads) void batch_gather_ex_kernel(GatherArgs a, GatherExtra e) {
+  batch_gather_body<T, true>(a, e);
+}
 
-extern "C" int feta_batch_gather(const feta_gather* dp, feta_stream_t stream) {
-  FETA_REQUIRE(dp != nullptr, "batch_gather: null descriptor");
-  const feta_gather& d = *dp;
+// the checks of both entry points, then the launch: with `e` the kernels that carry the fields of feta_gather_ex
+static int gather_launch(const feta_gather& d, const GatherExtra* e, feta_stream_t stream, const char* what) {
   FETA_REQUIRE(d.B > 0 && d.N > 0 && d.G > 0, "batch_gather: B = %d, N = %d, G = %d must be positive", d.B, d.N, d.G);
   FETA_REQUIRE(d.dtype == FETA_F32 || d.dtype == FETA_BF16, "batch_gather: unknown dtype %d", d.dtype);
   FETA_REQUIRE(d.ids && d.s_n && d.s_node_off, "batch_gather: ids, s_n and s_node_off are required");
@@ -151,13 +185,40 @@ extern "C" int feta_batch_gather(const feta_gather* dp, feta_stream_t stream) {
   if (d.pe && d.N % 4 == 0 && aligned16(d.s_pe) && out_ok(d.pe)) args.vec |= kGatherVecPe;
   if (d.u && d.K % 4 == 0 && aligned16(d.s_u) && aligned16(d.u)) args.vec |= kGatherVecU;
   if (d.lap && d.lap_dim % 4 == 0 && aligned16(d.s_lap) && aligned16(d.lap)) args.vec |= kGatherVecLap;
+  if (e && e->lhat && d.N % 4 == 0 && aligned16(e->s_lhat) && aligned16(e->lhat)) args.vec |= kGatherVecLhat;
   const dim3 grid(d.B, chunks), block(kGatherThreads);
-  if (bf) {
+  if (e) {
+    auto kern = bf ? batch_gather_ex_kernel<bf16_t> : batch_gather_ex_kernel<float>;
+    hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, args, *e);
+  } else if (bf) {
     auto kern = batch_gather_kernel<bf16_t>;
     hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, args);
   } else {
     auto kern = batch_gather_kernel<float>;
     hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, args);
   }
-  return check_launch("feta_batch_gather");
+  return check_launch(what);
+}
+
+}  // namespace feta
+
+using namespace feta;
+
+extern "C" int feta_batch_gather(const feta_gather* dp, feta_stream_t stream) {
+  FETA_REQUIRE(dp != nullptr, "batch_gather: null descriptor");
+  return gather_launch(*dp, nullptr, stream, "feta_batch_gather");
+}
+
+// feta_gather_ex repeats the fields of feta_gather in front of its own (one layout, checked here)
+static_assert(offsetof(feta_gather_ex, s_lhat) == sizeof(feta_gather) && offsetof(feta_gather_ex, labels) == offsetof(feta_gather, labels),
+              "feta_gather_ex must begin with the fields of feta_gather");
+
+extern "C" int feta_batch_gather_ex(const feta_gather_ex* dp, feta_stream_t stream) {
+  FETA_REQUIRE(dp != nullptr, "batch_gather_ex: null descriptor");
+  FETA_REQUIRE(!dp->lhat || (dp->s_lhat && dp->s_pe_off), "batch_gather_ex: lhat needs s_lhat and s_pe_off");
+  FETA_REQUIRE(!dp->lap_sign || dp->lap, "batch_gather_ex: lap_sign needs lap");
+  feta_gather d;
+  memcpy(&d, dp, sizeof d);
+  const GatherExtra e = {dp->s_lhat, dp->lhat, dp->lap_sign};
+  return gather_launch(d, &e, stream, "feta_batch_gather_ex");
 }

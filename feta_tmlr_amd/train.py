@@ -27,11 +27,16 @@ def warmup_lr(step, lr, warmup):
     return lr * warmup ** 0.5 * step ** -0.5
 
 
+def lap_signs(lap_dim, generator=None):
+    """[lap_dim] float32 of +1 / -1 on the host: one draw of the reference's per-batch sign flip."""
+    flip = torch.rand(lap_dim, generator=generator)
+    return torch.where(flip >= 0.5, torch.ones_like(flip), -torch.ones_like(flip))
+
+
 def lap_sign_flip(lap_pe, generator=None):
     """Random sign per Laplacian-PE column, one draw per batch
     (experiments/run_transformer_gengcn.py:126-131)."""
-    flip = torch.rand(lap_pe.shape[-1], generator=generator)
-    flip = torch.where(flip >= 0.5, torch.ones_like(flip), -torch.ones_like(flip))
+    flip = lap_signs(lap_pe.shape[-1], generator)
     return lap_pe * flip.to(lap_pe.device).unsqueeze(0)
 
 
@@ -272,23 +277,32 @@ class StoreTrainStep(GraphedTrainStep):
     mode as GraphedTrainStep (construction does not advance training: the warm-up and capture steps run on
     ``example_ids``, default the first graphs of the bucket).  Only FULL batches are captured: the ragged last batch of
     a bucket goes through ``store.batch(ids)`` and ``train_step(..., padded_node_labels=task == 'sbm')``.
-    filter_mode='spectral' only, and train.lap_sign_flip is not applied inside the captured step.
+    filter_mode='spectral' reads the store's u / lam, filter_mode='cheb' its lhat (``DeviceGraphStore(..., lhat=True)``;
+    the gather launch is then feta_batch_gather_ex), with either setting of heads_share_graph.
+    lap_sign_flip: the reference's random sign per Laplacian-PE column (lap_sign_flip above), drawn on the host for every
+    ``step(ids)`` with ``lap_signs(lap_dim, generator)`` and applied by the gather launch inside the hipGraph: one more
+    host-to-device copy of 4 * lap_dim bytes per step.  Warm-up and capture run with signs of +1 and draw nothing.
     dtype: storage type of x and pe as the gather emits them; the task shells embed fp32 x, so they keep float32 (a
     bf16-storage model rounds its rows and pe itself) and torch.bfloat16 is for a model that consumes bf16 x directly."""
 
     def __init__(self, task, model, criterion, optimizer, store, n_pad, batch_size, dtype=torch.float32,
-                 example_ids=None, warmup_iters=3):
+                 example_ids=None, warmup_iters=3, lap_sign_flip=False, generator=None):
         from .transformer.store import GatherBuffers
         self.task, self.model, self.criterion, self.optimizer = task, model, criterion, optimizer
-        if getattr(model.encoder, 'filter_mode', 'spectral') != 'spectral':
-            raise ValueError("StoreTrainStep runs filter_mode='spectral' models (the store holds no edge list)")
-        self.store = store
+        mode = getattr(model.encoder, 'filter_mode', 'spectral')
+        if mode not in ('spectral', 'cheb'):
+            raise ValueError("StoreTrainStep runs filter_mode='spectral' and 'cheb' models, got %r" % (mode,))
+        if mode == 'cheb' and store.lhat is None:
+            raise ValueError("a filter_mode='cheb' model needs the store's Laplacians: DeviceGraphStore(..., lhat=True)")
+        if lap_sign_flip and store.lap is None:
+            raise ValueError('lap_sign_flip needs a store with lap_dim')
+        self.store, self.generator = store, generator
         for group in optimizer.param_groups:
             if not group.get('capturable', False):
                 raise ValueError('StoreTrainStep needs make_optimizer(..., capturable=True)')
             if not torch.is_tensor(group['lr']):
                 group['lr'] = torch.tensor(float(group['lr']), device=store.device)
-        self.bufs = GatherBuffers(store, batch_size, n_pad, dtype)
+        self.bufs = GatherBuffers(store, batch_size, n_pad, dtype, lhat=mode == 'cheb', lap_sign=bool(lap_sign_flip))
         self._pinned, self._copied, self._turn = [None, None], [None, None], 0
         if example_ids is None:
             members = store.bucket_ids(n_pad)
@@ -312,7 +326,7 @@ class StoreTrainStep(GraphedTrainStep):
             self.loss = self._body()
         self._restore(snap)
 
-    def _set_ids(self, ids):
+    def _set_ids(self, ids, signs=None):
         import numpy as np
         ids = self.store.device_ids(ids) if torch.is_tensor(ids) else np.asarray(ids, np.int32)
         if tuple(ids.shape) != (self.bufs.bsz,):
@@ -320,18 +334,26 @@ class StoreTrainStep(GraphedTrainStep):
                              'store.batch and train_step)' % (self.bufs.bsz, tuple(ids.shape)))
         if torch.is_tensor(ids):
             self.bufs.ids.copy_(ids, non_blocking=True)
-            return
-        # one asynchronous host-to-device copy, straight into the static buffer, out of one of two pinned buffers used
-        # alternately (BatchStager's scheme: a buffer is refilled only after the copy enqueued from it has been read)
+            if signs is None:
+                return
+        # one asynchronous host-to-device copy per host operand (the ids, the signs), straight into the static buffer,
+        # out of one of two pinned buffer sets used alternately (BatchStager's scheme: a set is refilled only after the
+        # copies enqueued from it have been read)
         turn = self._turn
         self._turn ^= 1
         if self._pinned[turn] is None:
-            self._pinned[turn] = torch.empty(self.bufs.bsz, dtype=torch.int32, pin_memory=True)
+            sign_buf = None if self.bufs.lap_sign is None else torch.empty(self.bufs.lap_sign.shape, pin_memory=True)
+            self._pinned[turn] = (torch.empty(self.bufs.bsz, dtype=torch.int32, pin_memory=True), sign_buf)
             self._copied[turn] = torch.cuda.Event()
         else:
             self._copied[turn].synchronize()
-        self._pinned[turn].numpy()[:] = ids
-        self.bufs.ids.copy_(self._pinned[turn], non_blocking=True)
+        id_buf, sign_buf = self._pinned[turn]
+        if not torch.is_tensor(ids):
+            id_buf.numpy()[:] = ids
+            self.bufs.ids.copy_(id_buf, non_blocking=True)
+        if signs is not None:
+            sign_buf.copy_(signs)
+            self.bufs.lap_sign.copy_(sign_buf, non_blocking=True)
         self._copied[turn].record()
 
     def _body(self):
@@ -339,7 +361,8 @@ class StoreTrainStep(GraphedTrainStep):
         return super()._body()
 
     def __call__(self, ids):
-        self._set_ids(ids)
+        sign = self.bufs.lap_sign
+        self._set_ids(ids, None if sign is None else lap_signs(sign.shape[0], self.generator))
         self.graph.replay()
         if self.drop_calls:
             from .functional import DropoutState

@@ -6,15 +6,21 @@ already replaced the lists by vectorised gathers and the pickle by device kernel
 numpy gathers, ~10 host-to-device copies and the eigendecomposition of graphs that were decomposed in every epoch
 before.  ``DeviceGraphStore`` runs the stager ONCE per graph when it is built, packs what came out into flat device
 arrays, and ``feta_batch_gather`` (csrc/gather.hip) then builds the padded batch of any list of graph ids in one
-launch - inside a captured training step (``train.StoreTrainStep``) the host sends the ids and nothing else.
+launch - inside a captured training step (``train.StoreTrainStep``) the host sends the ids and nothing else (with
+``lap_sign_flip`` also the lap_dim signs of the batch).
 
 Store layout (G graphs, sumN nodes):
     x [sumN, F], degree [sumN], labels [G] (float32 / int64) or [sumN] int64 node labels, n [G] int32,
     node_off [G] int64, bucket [G] int32 (host), u [sumN, K], lam [G, K], lap [sumN, lap_dim],
     pe: graph g's n x n kernel at pe_off[g] with row pitch roundup4(n) (zero columns behind n): rows start on 16 bytes.
+    lhat (``lhat=True``): graph g's n x n scaled Laplacian, at the same pe_off[g] with the same pitch.
 
-Limits: filter_mode='spectral' only (no lhat, no edge list: edge_index / batch / feature_indices of the tuple are
-None), and a model that filters needs k_eig.
+Both filter modes are fed: filter_mode='spectral' reads cache.u / cache.lam (the store needs ``k_eig``), filter_mode='cheb'
+- the reference's operator and the constructor default of the models - reads cache.lhat (the store needs ``lhat=True``;
+``feta_batch_gather_ex`` emits it, and applies the per-batch sign flip of the Laplacian eigenvector features when it is
+given signs).  Limits: no edge list is kept, so edge_index / batch / feature_indices of the tuple are None and a cheb
+model on a store without lhat has nothing to build its Laplacian from; evaluation and ragged tail batches go through
+``store.batch``; bf16 storage with filter_mode='cheb' is refused by the models, here as everywhere.
 """
 import time
 
@@ -27,9 +33,11 @@ from .data import BUCKETS, BatchStager, GraphBatchCache
 
 class GatherBuffers:
     """The output tensors of one feta_batch_gather launch for a [B, N_pad] batch (a StoreTrainStep keeps one set as
-    the static inputs of its hipGraph)."""
+    the static inputs of its hipGraph).  lhat (default: when the store has it): [B, N_pad, N_pad] float32, the operand
+    of filter_mode='cheb'.  lap_sign: also a [lap_dim] float32 vector of +1, the factor per column of lap that the
+    launch applies (train.lap_signs).  Either one makes the launch feta_batch_gather_ex."""
 
-    def __init__(self, store, bsz, n_pad, dtype=torch.float32):
+    def __init__(self, store, bsz, n_pad, dtype=torch.float32, lhat=None, lap_sign=False):
         if dtype not in (torch.float32, torch.bfloat16):
             raise TypeError('float32 or bfloat16 x / pe, got %s' % dtype)
         dev = store.device
@@ -44,6 +52,12 @@ class GatherBuffers:
         self.u = new((bsz, n_pad, store.k), torch.float32) if store.u is not None else None
         self.lam = new((bsz, store.k), torch.float32) if store.u is not None else None
         self.lap = new((bsz, n_pad, store.lap_dim), torch.float32) if store.lap is not None else None
+        if lhat and store.lhat is None:
+            raise ValueError('lhat needs DeviceGraphStore(..., lhat=True)')
+        if lap_sign and store.lap is None:
+            raise ValueError('lap_sign needs DeviceGraphStore(..., lap_dim=...)')
+        self.lhat = new((bsz, n_pad, n_pad), torch.float32) if (store.lhat is not None and lhat is not False) else None
+        self.lap_sign = torch.ones((store.lap_dim,), dtype=torch.float32, device=dev) if lap_sign else None
         self.n_real = new((bsz,), torch.int32)
         self.node_off = new((bsz,), torch.int32)
         self.labels = new((bsz, n_pad) if store.node_labels else (bsz,), store.y.dtype)
@@ -53,7 +67,8 @@ class GatherBuffers:
         return (self.x, self.mask, self.pe, self.lap, self.degree, self.labels, None, None, None)
 
     def cache(self):
-        c = GraphBatchCache(n_real=self.n_real, node_off=self.node_off, n_pad=self.n_pad, u=self.u, lam=self.lam)
+        c = GraphBatchCache(n_real=self.n_real, node_off=self.node_off, n_pad=self.n_pad, u=self.u, lam=self.lam,
+                            lhat=self.lhat)
         if self.degree_rows is not None:
             c.extra['degree_rows'] = self.degree_rows
         return c
@@ -61,7 +76,9 @@ class GatherBuffers:
 
 class DeviceGraphStore:
     """``packed``: data.PackedGraphs of the split.  The other arguments are BatchStager's (pos_enc 'diffusion' | 'pstep',
-    k_eig eigenpairs for filter_mode='spectral', lap_dim Laplacian eigenvector features); every graph goes through
+    k_eig eigenpairs for filter_mode='spectral', lap_dim Laplacian eigenvector features); ``lhat=True`` also keeps every
+    graph's dense scaled Laplacian for filter_mode='cheb': 4 * n * roundup4(n) bytes per graph - about 2.2 KB per ZINC
+    graph on top of 6.9 KB, and as much as pe for any graph.  Every graph goes through
     ``BatchStager.stage`` once, at the padded size of its bucket and ``build_batch`` graphs at a time.  The kernels behind
     it work one workgroup per graph on the graph's own n x n block, so what is stored for a graph does not depend on the
     graphs it was staged with, and ``batch(ids)`` returns the tensors ``stage(ids)`` returns.
@@ -69,7 +86,7 @@ class DeviceGraphStore:
     ``build_seconds``: wall time of the construction (device work included); ``nbytes``: device bytes held."""
 
     def __init__(self, packed, device, buckets=BUCKETS, pos_enc=None, k_eig=None, lap_dim=None, beta=1.0, p=1,
-                 zero_diag=False, build_batch=256):
+                 zero_diag=False, build_batch=256, lhat=False):
         t0 = time.perf_counter()
         self.device = torch.device(device)
         dev = self.device
@@ -100,16 +117,19 @@ class DeviceGraphStore:
         sum_n = int(ns.sum())
         pitch = (ns + 3) & ~3
         sizes = pitch * ns
-        self.pe = self.pe_off = self.u = self.lam = self.lap = None
+        self.pe = self.pe_off = self.u = self.lam = self.lap = self.lhat = None
+        if pos_enc is not None or lhat:
+            self.pe_off = t(np.concatenate([[0], np.cumsum(sizes)])[:-1].astype(np.int64))   # n x n block offsets
         if pos_enc is not None:
-            self.pe_off = t(np.concatenate([[0], np.cumsum(sizes)])[:-1].astype(np.int64))
             self.pe = torch.zeros((int(sizes.sum()),), dtype=torch.float32, device=dev)
+        if lhat:
+            self.lhat = torch.zeros((int(sizes.sum()),), dtype=torch.float32, device=dev)
         if self.k is not None:
             self.u = torch.zeros((sum_n, self.k), dtype=torch.float32, device=dev)
             self.lam = torch.zeros((self.num_graphs, self.k), dtype=torch.float32, device=dev)
         if self.lap_dim is not None:
             self.lap = torch.zeros((sum_n, self.lap_dim), dtype=torch.float32, device=dev)
-        if self.pe is not None or self.u is not None or self.lap is not None:
+        if self.pe is not None or self.u is not None or self.lap is not None or self.lhat is not None:
             pitch_d = t(pitch)
             for n_pad in sorted(set(self.bucket.tolist())):
                 members = np.nonzero(self.bucket == n_pad)[0]
@@ -129,10 +149,17 @@ class DeviceGraphStore:
         r = torch.arange(n_pad, device=self.device)
         rows = r[None, :] < n[:, None]                                       # [b, N] real nodes
         dst_rows = (self.node_off[gids][:, None] + r[None, :])[rows]
-        if self.pe is not None:
+        if self.pe is not None or self.lhat is not None:
             real = rows[:, :, None] & rows[:, None, :]
-            dst = self.pe_off[gids][:, None, None] + r[None, :, None] * pitch[gids][:, None, None] + r[None, None, :]
-            self.pe[dst[real]] = batch9[2][real]
+            dst = (self.pe_off[gids][:, None, None] + r[None, :, None] * pitch[gids][:, None, None] + r[None, None, :])[real]
+        if self.pe is not None:
+            self.pe[dst] = batch9[2][real]
+        if self.lhat is not None:
+            lhat = cache.lhat          # attach_device_spectrum left it there when the stager computed a spectrum
+            if lhat is None:
+                from .. import functional as FF
+                lhat = FF.lhat_from_edges(batch9[6], batch9[7], cache.node_off, n.shape[0], n_pad)
+            self.lhat[dst] = lhat[real]
         if self.u is not None:
             self.u[dst_rows] = cache.u[rows]
             self.lam[gids] = cache.lam
@@ -141,7 +168,8 @@ class DeviceGraphStore:
 
     @property
     def nbytes(self):
-        ts = (self.x, self.degree, self.y, self.n, self.node_off, self.pe, self.pe_off, self.u, self.lam, self.lap)
+        ts = (self.x, self.degree, self.y, self.n, self.node_off, self.pe, self.pe_off, self.u, self.lam, self.lap,
+              self.lhat)
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     def bucket_ids(self, n_pad):
@@ -169,22 +197,28 @@ class DeviceGraphStore:
         return torch.from_numpy(np.ascontiguousarray(np.asarray(ids, np.int32))).to(self.device)
 
     def gather_into(self, bufs, ids=None):
-        """one feta_batch_gather launch on the current stream: the batch of ``ids`` (default: bufs.ids) into bufs"""
+        """one launch on the current stream: the batch of ``ids`` (default: bufs.ids) into bufs - feta_batch_gather, or
+        feta_batch_gather_ex when bufs carries lhat or lap_sign"""
         ids = bufs.ids if ids is None else ids
         abi, stream = _lib.backend(self.x, ids)
-        abi.batch_gather(self.num_graphs, bufs.bsz, bufs.n_pad, stream, f=self.f, k=self.k or 0, lap_dim=self.lap_dim or 0,
-                         dtype=abi._dt_of(bufs.dtype), label_kind=self.label_kind,
-                         s_x=self.x, s_degree=self.degree, s_labels=self.y, s_n=self.n, s_node_off=self.node_off,
-                         s_pe=self.pe, s_pe_off=self.pe_off, s_u=self.u, s_lam=self.lam, s_lap=self.lap, ids=ids,
-                         x=bufs.x, mask=bufs.mask, degree=bufs.degree, degree_rows=bufs.degree_rows, pe=bufs.pe, u=bufs.u,
-                         lam=bufs.lam, lap=bufs.lap, n_real=bufs.n_real, node_off=bufs.node_off, labels=bufs.labels)
+        kw = dict(f=self.f, k=self.k or 0, lap_dim=self.lap_dim or 0, dtype=abi._dt_of(bufs.dtype), label_kind=self.label_kind,
+                  s_x=self.x, s_degree=self.degree, s_labels=self.y, s_n=self.n, s_node_off=self.node_off,
+                  s_pe=self.pe, s_pe_off=self.pe_off, s_u=self.u, s_lam=self.lam, s_lap=self.lap, ids=ids,
+                  x=bufs.x, mask=bufs.mask, degree=bufs.degree, degree_rows=bufs.degree_rows, pe=bufs.pe, u=bufs.u,
+                  lam=bufs.lam, lap=bufs.lap, n_real=bufs.n_real, node_off=bufs.node_off, labels=bufs.labels)
+        if bufs.lhat is not None or bufs.lap_sign is not None:
+            abi.batch_gather_ex(self.num_graphs, bufs.bsz, bufs.n_pad, stream, lhat=bufs.lhat, lap_sign=bufs.lap_sign,
+                                s_lhat=self.lhat if bufs.lhat is not None else None, **kw)
+        else:
+            abi.batch_gather(self.num_graphs, bufs.bsz, bufs.n_pad, stream, **kw)
         return bufs
 
-    def batch(self, ids, n_pad=None, dtype=torch.float32):
+    def batch(self, ids, n_pad=None, dtype=torch.float32, lhat=None):
         """-> (batch9, cache) of the graphs ``ids`` in the layout of BatchStager.stage: x, mask, pe, lap, degree, labels
-        and a cache with n_real, node_off, u, lam and extra['degree_rows']; edge_index, batch and feature_indices are
-        None (filter_mode='spectral' with cache.u reads none of them), node labels come padded [B, N_pad] with -100.
-        n_pad: default the largest bucket among the ids (host ids only).  dtype: type of x and pe."""
+        and a cache with n_real, node_off, u, lam, lhat and extra['degree_rows']; edge_index, batch and feature_indices
+        are None (filter_mode='spectral' with cache.u and filter_mode='cheb' with cache.lhat read none of them), node
+        labels come padded [B, N_pad] with -100.  n_pad: default the largest bucket among the ids (host ids only).
+        dtype: type of x and pe.  lhat: emit cache.lhat (default: whenever the store has it)."""
         if n_pad is None:
             if torch.is_tensor(ids):
                 raise ValueError('n_pad is needed with device-resident ids')
@@ -192,5 +226,5 @@ class DeviceGraphStore:
         ids = self.device_ids(ids)
         if ids.dim() != 1 or ids.shape[0] == 0:
             raise ValueError('ids must be a non-empty 1-d sequence')
-        bufs = self.gather_into(GatherBuffers(self, ids.shape[0], n_pad, dtype), ids)
+        bufs = self.gather_into(GatherBuffers(self, ids.shape[0], n_pad, dtype, lhat=lhat), ids)
         return bufs.batch9(), bufs.cache()

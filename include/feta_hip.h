@@ -1043,7 +1043,7 @@ typedef struct feta_gather {
   const int32_t* s_n;          /* [G] node counts */
   const int64_t* s_node_off;   /* [G] first row of each graph */
   const float* s_pe;           /* flat, see above */
-  const int64_t* s_pe_off;     /* [G] */
+  const int64_t* s_pe_off;     /* [G] n x n block offsets (feta_gather_ex: shared with s_lhat) */
   const float* s_u;            /* [sumN,K] */
   const float* s_lam;          /* [G,K] */
   const float* s_lap;          /* [sumN,lap_dim] */
@@ -1064,6 +1064,49 @@ typedef struct feta_gather {
   void* labels;                /* label_kind */
 } feta_gather;
 int feta_batch_gather(const feta_gather* d, feta_stream_t stream);
+
+/* ... with the dense scaled Laplacian of filter_mode='cheb' and the per-batch sign flip of the Laplacian eigenvector
+ * features (additive, like feta_encoder_infer_ex): the fields of feta_gather, in its order, and behind them
+ *   s_lhat    graph g's n x n block of Lhat (feta_lhat_from_edges) in the geometry of s_pe: it starts at
+ *             s_lhat + s_pe_off[g], row pitch n rounded up to a multiple of 4, zero columns behind n.  s_pe_off holds
+ *             "n x n block offsets" shared by both arrays and is required whenever pe or lhat is requested.
+ *   lhat      [B,N,N], ALWAYS fp32 (the filter stage is fp32 on both storage types): rows and columns behind n_real
+ *             zero, the whole block zero for an empty slot; every element is written on every launch.  16-byte vectors
+ *             when N % 4 == 0, both pointers are 16-byte aligned and the block offset is a multiple of 4.
+ *   lap_sign  [lap_dim] on the device or NULL: lap[b,i,c] = s_lap[.,c] * lap_sign[c] (train.lap_sign_flip, one draw per
+ *             batch: experiments/run_transformer_gengcn.py:126-131); the padding stays zero.  Needs lap.
+ * With s_lhat = lhat = lap_sign = NULL it writes what feta_batch_gather writes, bit for bit.  Same grid, no LDS. */
+typedef struct feta_gather_ex {
+  const float* s_x;
+  const float* s_degree;
+  const void* s_labels;
+  const int32_t* s_n;
+  const int64_t* s_node_off;
+  const float* s_pe;
+  const int64_t* s_pe_off;     /* [G] n x n block offsets, of s_pe and of s_lhat */
+  const float* s_u;
+  const float* s_lam;
+  const float* s_lap;
+  const int32_t* ids;
+  int G, B, N, F, K, lap_dim;
+  int dtype;
+  int label_kind;
+  void* x;
+  void* mask;
+  float* degree;
+  float* degree_rows;
+  void* pe;
+  float* u;
+  float* lam;
+  float* lap;
+  int32_t* n_real;
+  int32_t* node_off;
+  void* labels;
+  const float* s_lhat;         /* flat, see above */
+  float* lhat;                 /* [B,N,N] fp32 */
+  const float* lap_sign;       /* [lap_dim] or NULL */
+} feta_gather_ex;
+int feta_batch_gather_ex(const feta_gather_ex* d, feta_stream_t stream);
 
 #ifdef __cplusplus
 }
