@@ -387,6 +387,22 @@ SIGNATURES['feta_batch_gather_ex'] = ([C.POINTER(GatherEx), _S], C.c_int)
 
 LABELS_NONE, LABELS_GRAPH_F32, LABELS_GRAPH_I64, LABELS_NODE_I64 = 0, 1, 2, 3      # FETA_LABELS_*
 
+
+class Readout(C.Structure):
+    """struct feta_readout (include/feta_hip.h) - field order must match the header."""
+    _fields_ = [
+        ('y', _F), ('row_sb', C.c_int64), ('row_sn', C.c_int64), ('n_real', _I), ('ids', _I), ('count', _I),
+        ('labels', C.c_void_p), ('w1', _F), ('b1', _F), ('w2', _F), ('b2', _F), ('scores', _F), ('terms', _F),
+        ('B', C.c_int), ('N', C.c_int), ('G', C.c_int), ('C', C.c_int), ('d_model', C.c_int),
+        ('label_kind', C.c_int), ('loss_kind', C.c_int), ('slope', C.c_float),
+    ]
+
+
+SIGNATURES['feta_readout_eval_supported'] = ([C.c_int, C.c_int], C.c_int)
+SIGNATURES['feta_readout_eval'] = ([C.POINTER(Readout), _S], C.c_int)
+
+LOSS_L1, LOSS_BCE_LOGITS, LOSS_CE = 0, 1, 2      # FETA_LOSS_*
+
 ABI_VERSION = 13
 
 
@@ -1103,6 +1119,22 @@ class Abi:
         _same_dtype(torch.float32, *(ptrs.get(key) for key in ('s_lhat', 'lhat', 'lap_sign')))
         d = self._gather_desc(GatherEx, g, b, n, f, k, lap_dim, dtype, label_kind, ptrs)
         self._check(self.lib.feta_batch_gather_ex(C.byref(d), stream), 'feta_batch_gather_ex')
+
+    def readout_eval_supported(self, d_model, c):
+        return bool(self.lib.feta_readout_eval_supported(d_model, c))
+
+    def readout_eval(self, b, n, g, c, stream, d_model=64, row_sb=0, row_sn=0, label_kind=LABELS_GRAPH_F32,
+                     loss_kind=LOSS_L1, slope=0.0, **ptrs):
+        """feta_readout_eval: pooling, classifier, scores and loss / metric terms of the live slots of a [b, n] batch out
+        of a split of g graphs.  Tensor-valued keyword arguments become the descriptor's pointers (y, n_real, ids, count,
+        labels, w1, b1, w2, b2, scores, terms); row_sb / row_sn: element strides of y's graph and node index."""
+        _same_dtype(torch.float32, *(ptrs.get(k) for k in ('y', 'w1', 'b1', 'w2', 'b2', 'scores', 'terms')))
+        _same_dtype(torch.int32, *(ptrs.get(k) for k in ('n_real', 'ids', 'count')))
+        d = Readout()
+        d.B, d.N, d.G, d.C, d.d_model, d.row_sb, d.row_sn = b, n, g, c, d_model, row_sb, row_sn
+        d.label_kind, d.loss_kind, d.slope = label_kind, loss_kind, slope
+        _fill(d, ptrs)
+        self._check(self.lib.feta_readout_eval(C.byref(d), stream), 'feta_readout_eval')
 
 
 def bind(cdll):

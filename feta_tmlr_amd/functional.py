@@ -6,7 +6,7 @@ produced in place: no transposes, no gathers, no scatter into zero-initialised b
 """
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._abi import CoeffSavedReq, LinDwReq
 
 
@@ -1111,3 +1111,42 @@ def spectral_kernel(u, lam, n_real, kind='diffusion', beta=1.0, p=1, lam_offset=
     abi.spectral_kernel(u.contiguous(), lam.contiguous(), n_real.contiguous(), SPECTRAL_MODES[kind],
                         float(beta), int(p), float(lam_offset), bool(zero_diag), out, stream)
     return out
+
+
+LOSS_KINDS = {'l1': _abi.LOSS_L1, 'bce_logits': _abi.LOSS_BCE_LOGITS, 'ce': _abi.LOSS_CE}
+
+
+def readout_eval(y, n_real, ids, count, labels, w1, b1, w2, b2, scores, terms, loss_kind, slope=0.0):
+    """Graph-level readout of an evaluation batch in one launch (feta_readout_eval), forward only: for every slot
+    b < count[0] the masked mean of the rows y[:n_real[b], b] ([N, B, 64] float32, any row strides - a view is read in
+    place), Linear(w1, b1) - act - Linear(w2, b2) with act(v) = v if v > 0 else slope * v, the logits into
+    scores[ids[b]] ([G, C]) and the loss / metric terms of ``loss_kind`` ('l1' | 'bce_logits' | 'ce', include/feta_hip.h)
+    from labels[b] (float32 or int64) into terms[ids[b]] ([G, 4]).  ids (int32, the first B elements) and count (int32,
+    one element) live on the device; slots from count[0] on write nothing.  Returns (scores, terms)."""
+    if loss_kind not in LOSS_KINDS:
+        raise ValueError('unknown loss_kind %r' % (loss_kind,))
+    abi, stream = _lib.backend(y, n_real, ids, count, labels, w1, b1, w2, b2, scores, terms)
+    if y.dim() != 3 or y.stride(2) != 1:
+        raise ValueError('readout_eval: y must be [N, B, d] with dense columns, got %s with strides %s' % (tuple(y.shape), y.stride()))
+    n, b, d = y.shape
+    if scores.dim() != 2 or terms.dim() != 2 or terms.shape != (scores.shape[0], 4):
+        raise ValueError('readout_eval: scores [G, C] and terms [G, 4], got %s and %s' % (tuple(scores.shape), tuple(terms.shape)))
+    g, c = scores.shape
+    if not abi.readout_eval_supported(d, c):
+        raise ValueError('readout_eval: d = %d, C = %d (the kernel has d = 64 and 1 <= C <= 64)' % (d, c))
+    for name, t, shape in (('n_real', n_real, (b,)), ('w1', w1, (d, d)), ('b1', b1, (d,)), ('w2', w2, (c, d)), ('b2', b2, (c,))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError('readout_eval: %s must be contiguous %s, got %s' % (name, shape, tuple(t.shape)))
+    for name, t, least in (('ids', ids, b), ('count', count, 1), ('labels', labels, b)):
+        if t.numel() < least or not t.is_contiguous():
+            raise ValueError('readout_eval: %s must be contiguous with at least %d elements' % (name, least))
+    if not (scores.is_contiguous() and terms.is_contiguous()):
+        raise ValueError('readout_eval: scores and terms must be contiguous')
+    if labels.dtype not in (torch.float32, torch.int64):
+        raise TypeError('readout_eval: float32 or int64 labels, got %s' % labels.dtype)
+    kind = _abi.LABELS_GRAPH_F32 if labels.dtype == torch.float32 else _abi.LABELS_GRAPH_I64
+    # (the stride of a size-1 dim is arbitrary and multiplies index 0 only)
+    abi.readout_eval(b, n, g, c, stream, d_model=d, row_sb=y.stride(1) if b > 1 else 0, row_sn=y.stride(0) if n > 1 else 0,
+                     label_kind=kind, loss_kind=LOSS_KINDS[loss_kind], slope=float(slope), y=y, n_real=n_real, ids=ids,
+                     count=count, labels=labels, w1=w1, b1=b1, w2=w2, b2=b2, scores=scores, terms=terms)
+    return scores, terms

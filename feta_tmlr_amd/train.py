@@ -13,7 +13,9 @@ collate already emits device tensors), dataset download and CSV logging.
 
 ``GraphedTrainStep`` is the MI355X form of the loop body: forward, loss, backward and the optimiser
 update captured once per padded size into a hipGraph and replayed - the reference pays ~10^3 kernel
-launches and a host sync (`.cpu()` at transformer/models.py:246) per step.
+launches and a host sync (`.cpu()` at transformer/models.py:246) per step.  ``StoreTrainStep`` feeds it from a
+device-resident split, and ``StoreEvaluator`` / ``StoreEvalStep`` are the eval_epoch of the graph-level tasks in the
+same form: one captured forward-only graph per bucket, one host read per split (``evaluate`` is the eager form).
 """
 import torch
 from torch import nn
@@ -435,3 +437,236 @@ def _evaluate(task, model, criterion, batches):
     elif task == 'molhiv':
         res['rocauc'] = rocauc(torch.cat(scores), torch.cat(labels_all))
     return res
+
+
+_USE_EAGER = 'run it through store.batch and train.evaluate'
+
+
+def _readout_plan(task, model, criterion, store):
+    """-> (loss_kind of functional.readout_eval, slope of the classifier's activation, d_model, nb_class, filter_mode) of a
+    graph-level shell whose evaluation a StoreEvalStep on ``store`` can run; ValueError where it cannot (everything that
+    does not depend on the padded size)."""
+    if task == 'sbm':
+        raise ValueError("task 'sbm' has node-level logits and a per-batch confusion-matrix accuracy: " + _USE_EAGER)
+    if task not in ('zinc', 'tu', 'molhiv'):
+        raise ValueError('unknown task %r' % (task,))
+    head = getattr(model, 'classifier', None)
+    if (not hasattr(model, 'encoder_rows') or not isinstance(head, nn.Sequential) or len(head) != 3
+            or not isinstance(head[0], nn.Linear) or not isinstance(head[2], nn.Linear)):
+        raise ValueError('the model is not a graph-level shell with a Linear - activation - Linear classifier: ' + _USE_EAGER)
+    if isinstance(head[1], nn.ReLU):
+        slope = 0.0
+    elif isinstance(head[1], nn.LeakyReLU):
+        slope = float(head[1].negative_slope)        # (nn.LeakyReLU(True) of the molhiv shell: 1.0, the identity)
+    else:
+        raise ValueError('classifier activation %s: ReLU or LeakyReLU only; %s' % (type(head[1]).__name__, _USE_EAGER))
+    d, c = head[0].in_features, head[2].out_features
+    kind = 'l1' if task == 'zinc' else 'bce_logits' if (task == 'molhiv' or c == 1) else 'ce'
+    if criterion is not None and task != 'molhiv':       # (task_loss does not read the criterion of 'molhiv')
+        want = {'l1': nn.L1Loss, 'bce_logits': nn.BCEWithLogitsLoss, 'ce': nn.CrossEntropyLoss}[kind]
+        if not isinstance(criterion, want):
+            raise ValueError('task %r with %d outputs is evaluated with %s, got %s: %s'
+                             % (task, c, want.__name__, type(criterion).__name__, _USE_EAGER))
+        if (getattr(criterion, 'weight', None) is not None or getattr(criterion, 'pos_weight', None) is not None
+                or getattr(criterion, 'label_smoothing', 0.0) != 0.0):
+            raise ValueError('a criterion with class weights or label smoothing: ' + _USE_EAGER)
+        if criterion.reduction != 'mean':
+            raise ValueError("a criterion with reduction %r (the evaluation averages per batch: 'mean'): %s"
+                             % (criterion.reduction, _USE_EAGER))
+    from . import _lib
+    if not _lib.backend(store.x)[0].readout_eval_supported(d, c):
+        raise ValueError('feta_readout_eval has d_model = 64 and at most 64 outputs, the classifier has %d and %d: %s'
+                         % (d, c, _USE_EAGER))
+    mode = getattr(model.encoder, 'filter_mode', None)
+    if mode not in ('spectral', 'cheb'):
+        raise ValueError('StoreEvalStep runs the FeTA encoder (filter_mode spectral or cheb): ' + _USE_EAGER)
+    if mode == 'cheb' and store.lhat is None:
+        raise ValueError("a filter_mode='cheb' model needs the store's Laplacians, DeviceGraphStore(..., lhat=True); or "
+                         + _USE_EAGER)
+    if mode == 'spectral' and store.u is None:
+        raise ValueError("a filter_mode='spectral' model needs the store's eigenpairs, DeviceGraphStore(..., k_eig=...)")
+    if store.node_labels:
+        raise ValueError('a store of node labels: ' + _USE_EAGER)
+    return kind, slope, d, c, mode
+
+
+class StoreEvalStep:
+    """The evaluation of one padded batch of a ``transformer.store.DeviceGraphStore`` as ONE captured hipGraph, under
+    ``torch.inference_mode()`` with the model in ``eval()``: feta_batch_gather -> embedding (+ embedding_lap_pos_enc, no
+    sign flip) -> the encoder (the one-launch stack feta_encoder_infer[_ex] and the filter stage) -> feta_readout_eval,
+    which leaves the logits of every graph in ``scores`` [G, C] and its loss / metric terms in ``terms`` [G, 4], both
+    indexed by the graph's id in the store.  One instance per (bucket n_pad, batch_size); nothing is mutated, so
+    construction needs no snapshot, and ``model.training`` is what it was afterwards.
+
+    ``step(ids)``: 1 <= len(ids) <= batch_size host ids.  The static id buffer holds batch_size + 1 int32: the gather's
+    ids and, behind them, the number of live slots, which the readout reads on the device.  A short batch is padded with
+    ids[0]: the padded slots hold a real graph, so no kernel meets an empty graph, and the readout skips them.  All of it
+    travels in one asynchronous copy out of alternating pinned buffers; a step does not wait for the device.
+
+    The hipGraph holds the ADDRESSES of the parameters and of the BatchNorm running statistics; the optimiser and the
+    training BatchNorm update them in place, so a step captured once reports the current model.
+
+    ValueError (the path to use instead is store.batch + train.evaluate): task 'sbm'; a stack that
+    fused_stack.infer_supported refuses at this n_pad (N_pad > 64, ...); a classifier feta_readout_eval_supported
+    refuses; a criterion with class weights or another reduction than 'mean'; a filter_mode='cheb' model on a store
+    without lhat.  On a CPU store - the host emulation of the tests - nothing is captured and a step runs its body."""
+
+    def __init__(self, task, model, store, n_pad, batch_size, scores, terms, dtype=torch.float32, criterion=None,
+                 warmup_iters=3):
+        from .fused_stack import infer_supported
+        from .transformer.store import GatherBuffers
+        self.task, self.model, self.store = task, model, store
+        self.loss_kind, self.slope, d, c, mode = _readout_plan(task, model, criterion, store)
+        enc = model.encoder
+        if tuple(scores.shape) != (store.num_graphs, c) or tuple(terms.shape) != (store.num_graphs, 4):
+            raise ValueError('scores [%d, %d] and terms [%d, 4], got %s and %s'
+                             % (store.num_graphs, c, store.num_graphs, tuple(scores.shape), tuple(terms.shape)))
+        head = model.classifier
+        self.weights = tuple(None if p is None else p.detach() for p in (head[0].weight, head[0].bias, head[2].weight, head[2].bias))
+        if not all(p is None or p.is_contiguous() for p in self.weights):
+            raise ValueError('the classifier parameters must be contiguous (they are read in place)')
+        self.bsz, self.scores, self.terms = int(batch_size), scores, terms
+        self.bufs = GatherBuffers(store, self.bsz, n_pad, dtype, lhat=mode == 'cheb')
+        self.ids = torch.zeros((self.bsz + 1,), dtype=torch.int32, device=store.device)
+        self.bufs.ids = self.ids[:self.bsz]          # the gather reads the front of the step's one static id buffer
+        self.cache = self.bufs.cache()
+        self._pinned, self._copied, self._turn = [None, None], [None, None], 0
+        self.graph = None
+        was_training = model.training
+        model.eval()
+        try:
+            if not (getattr(enc, 'fused_stack', False) and enc.last_layer_filter
+                    and enc.layers[0].storage_dtype == enc.storage_dtype and infer_supported(enc.layers, int(n_pad), d)):
+                raise ValueError('the encoder stack has no one-launch inference form at N_pad = %d (d_model = 64, 4 or 8 '
+                                 'heads, N_pad <= 64, ...): %s' % (n_pad, _USE_EAGER))
+            members = store.bucket_ids(n_pad)
+            if len(members) == 0:
+                raise ValueError('no graph of the store is padded to %d' % n_pad)
+            if store.device.type == 'cuda':
+                self._send(members[:self.bsz])
+                with torch.inference_mode():
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        for _ in range(warmup_iters):
+                            self._body()
+                    torch.cuda.current_stream().wait_stream(side)
+                    self.graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph):
+                        self._body()
+        finally:
+            model.train(was_training)
+
+    def _send(self, ids):
+        import numpy as np
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        k = len(ids)
+        if not 1 <= k <= self.bsz:
+            raise ValueError('this step takes 1 to %d ids, got %d (StoreEvaluator cuts a split into batches)' % (self.bsz, k))
+        if self.store.device.type != 'cuda':
+            host = self.ids.numpy()
+        else:
+            # one asynchronous copy of the ids AND the count out of one of two pinned buffers used alternately
+            # (StoreTrainStep._set_ids: a buffer is refilled only after the copy enqueued from it has been read)
+            turn = self._turn
+            self._turn ^= 1
+            if self._pinned[turn] is None:
+                self._pinned[turn] = torch.empty(self.bsz + 1, dtype=torch.int32, pin_memory=True)
+                self._copied[turn] = torch.cuda.Event()
+            else:
+                self._copied[turn].synchronize()
+            host = self._pinned[turn].numpy()
+        host[:k] = ids
+        host[k:self.bsz] = ids[0]
+        host[self.bsz] = k
+        if self.store.device.type == 'cuda':
+            self.ids.copy_(self._pinned[turn], non_blocking=True)
+            self._copied[turn].record()
+
+    def _body(self):
+        from . import functional as FF
+        bufs = self.store.gather_into(self.bufs)
+        rows, _ = self.model.encoder_rows(bufs.x, None, None, None, bufs.mask, bufs.pe, bufs.lap, bufs.degree,
+                                          graph_cache=self.cache)
+        w1, b1, w2, b2 = self.weights
+        FF.readout_eval(rows, bufs.n_real, self.ids, self.ids[self.bsz:], bufs.labels, w1, b1, w2, b2, self.scores,
+                        self.terms, self.loss_kind, self.slope)
+
+    def __call__(self, ids):
+        self._send(ids)
+        if self.graph is not None:
+            self.graph.replay()
+            return
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.inference_mode():
+                self._body()
+        finally:
+            self.model.train(was_training)
+
+    step = __call__
+
+
+class StoreEvaluator:
+    """The reference's eval_epoch of a whole split out of a ``DeviceGraphStore``: one ``StoreEvalStep`` per bucket (built
+    on first use), one small copy and one replay per batch - ragged tails included -, ONE device read per call.
+    ``evaluate(ids=None)`` walks ``store.epoch(batch_size)`` - with ``ids`` only those graphs, in the same order - and
+    returns the dict ``evaluate`` (below the training steps) returns for the same cut into batches (``batches(ids)``):
+    'loss' is the sample-weighted mean of the per-batch means ('molhiv': a batch's mean runs over its labelled graphs), plus
+    'mae' and 'mse' (zinc), 'acc' (tu) or 'rocauc' (molhiv, ``rocauc`` on the [G] scores and the store's labels).  The
+    reductions run on the host in fp64 over the per-graph rows of ``terms``; ``scores`` [G, C] and ``terms`` [G, 4] stay on the
+    device, indexed by graph id.  Raises what StoreEvalStep raises, the task and criterion checks at construction."""
+
+    def __init__(self, task, model, criterion, store, batch_size, dtype=torch.float32):
+        self.task, self.model, self.criterion, self.store = task, model, criterion, store
+        self.batch_size, self.dtype = int(batch_size), dtype
+        c = _readout_plan(task, model, criterion, store)[3]
+        self.scores = torch.zeros((store.num_graphs, c), dtype=torch.float32, device=store.device)
+        self.terms = torch.zeros((store.num_graphs, 4), dtype=torch.float32, device=store.device)
+        self.labels = store.y.detach().cpu()        # (read once: what rocauc ranks the scores against)
+        self.steps = {}
+
+    def batches(self, ids=None):
+        """-> [(n_pad, ids int32)]: store.epoch(batch_size), restricted to ``ids`` when given"""
+        import numpy as np
+        if ids is None:
+            return list(self.store.epoch(self.batch_size))
+        ids = np.unique(np.asarray(ids, np.int64))
+        if len(ids) and (ids[0] < 0 or ids[-1] >= self.store.num_graphs):
+            raise ValueError('ids outside the store of %d graphs' % self.store.num_graphs)
+        cut = []
+        for n_pad, members in self.store.epoch(1 << 30):
+            members = members[np.isin(members, ids)]
+            cut += [(n_pad, members[s:s + self.batch_size]) for s in range(0, len(members), self.batch_size)]
+        return cut
+
+    def step_for(self, n_pad):
+        if n_pad not in self.steps:
+            self.steps[n_pad] = StoreEvalStep(self.task, self.model, self.store, n_pad, self.batch_size, self.scores,
+                                              self.terms, self.dtype, criterion=self.criterion)
+        return self.steps[n_pad]
+
+    def evaluate(self, ids=None):
+        import numpy as np
+        cut = self.batches(ids)
+        if not cut:
+            raise ValueError('nothing to evaluate')
+        for n_pad, batch in cut:
+            self.step_for(n_pad)(batch)
+        host = torch.cat((self.scores, self.terms), dim=1).cpu().double()       # the one device read
+        terms = host[:, self.scores.shape[1]:]
+        walked = torch.from_numpy(np.concatenate([batch for _, batch in cut]).astype(np.int64))
+        n_sample = len(walked)
+        loss = 0.0
+        for _, batch in cut:
+            rows = terms[torch.from_numpy(batch.astype(np.int64))]
+            loss += float(rows[:, 0].sum() / rows[:, 3].sum()) * len(batch)      # (weight 0: an unlabelled molhiv graph)
+        res = {'loss': loss / n_sample}
+        if self.task == 'zinc':
+            res.update(mae=res['loss'], mse=float(terms[walked, 1].sum()) / n_sample)
+        elif self.task == 'tu':
+            res['acc'] = float(terms[walked, 1].sum()) / n_sample
+        elif self.task == 'molhiv':
+            res['rocauc'] = rocauc(host[walked, 0], self.labels[walked])
+        return res

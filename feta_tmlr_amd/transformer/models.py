@@ -412,14 +412,22 @@ class DiffGraphTransformerGenGCN(nn.Module):
         self.classifier = nn.Sequential(nn.Linear(d_model, d_model), nn.ReLU(True),
                                         nn.Linear(d_model, nb_class))
 
-    def forward(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None,
-                degree=None, regularization=0.0, return_filter_coeff=False, graph_cache=None):
+    def encoder_rows(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None, degree=None,
+                     graph_cache=None):
+        """-> (encoder output rows [N, B, d], filter coefficients): ``forward`` up to, not including, the pooling -
+        what a fused readout (functional.readout_eval, train.StoreEvalStep) consumes in place."""
         output = input_embedding(self.embedding, x.permute(1, 0, 2))                              # :521-522
         if self.lap_pos_enc and x_lap_pos_enc is not None:
             output = output + self.embedding_lap_pos_enc(x_lap_pos_enc.transpose(0, 1))   # :523-526
         output, attn, filter_coeff = self.encoder(output, pe, edge_index, feature_indices, batch,
                                                   degree=degree, src_key_padding_mask=masks,
                                                   graph_cache=graph_cache)       # :527
+        return output, filter_coeff
+
+    def forward(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None,
+                degree=None, regularization=0.0, return_filter_coeff=False, graph_cache=None):
+        output, filter_coeff = self.encoder_rows(x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc, degree,
+                                                 graph_cache)
         pooled = self.pooling(output.permute(1, 0, 2), masks)                    # :528,532
         reg = 0
         if regularization > 0:
@@ -520,8 +528,10 @@ class DiffGraphTransformerGenGCNMolHiv(nn.Module):
                                         nn.Linear(d_model, nb_class))            # :635-639
         self.sigmoid = nn.Sigmoid()
 
-    def forward(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None,
-                degree=None, regularization=0.0, return_filter_coeff=False, graph_cache=None):
+    def encoder_rows(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None, degree=None,
+                     graph_cache=None):
+        """-> (encoder output rows [N, B, d], filter coefficients or None): ``forward`` up to, not including, the
+        pooling (DiffGraphTransformerGenGCN.encoder_rows)."""
         emb = self.embedding(x.reshape(-1, x.shape[-1]).to(torch.long))          # :645-646
         output = emb.reshape(x.shape[0], x.shape[1], self.d_model).permute(1, 0, 2)   # :648,667
         if self.lap_pos_enc and x_lap_pos_enc is not None:
@@ -533,6 +543,12 @@ class DiffGraphTransformerGenGCNMolHiv(nn.Module):
             output, attn, filter_coeff = self.encoder(output, pe, edge_index, feature_indices, batch,
                                                       degree=degree, src_key_padding_mask=masks,
                                                       graph_cache=graph_cache)   # :674
+        return output, filter_coeff
+
+    def forward(self, x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc=None,
+                degree=None, regularization=0.0, return_filter_coeff=False, graph_cache=None):
+        output, filter_coeff = self.encoder_rows(x, edge_index, batch, feature_indices, masks, pe, x_lap_pos_enc, degree,
+                                                 graph_cache)
         pooled = self.pooling(output.permute(1, 0, 2), masks)                    # :675,679
         reg = self.regularisation(filter_coeff) if regularization > 0 else 0     # :715-718
         cls_out = self.classifier(pooled)                                        # :720

@@ -18,9 +18,13 @@ Store layout (G graphs, sumN nodes):
 Both filter modes are fed: filter_mode='spectral' reads cache.u / cache.lam (the store needs ``k_eig``), filter_mode='cheb'
 - the reference's operator and the constructor default of the models - reads cache.lhat (the store needs ``lhat=True``;
 ``feta_batch_gather_ex`` emits it, and applies the per-batch sign flip of the Laplacian eigenvector features when it is
-given signs).  Limits: no edge list is kept, so edge_index / batch / feature_indices of the tuple are None and a cheb
-model on a store without lhat has nothing to build its Laplacian from; evaluation and ragged tail batches go through
-``store.batch``; bf16 storage with filter_mode='cheb' is refused by the models, here as everywhere.
+given signs).  A split is evaluated from the store in captured steps too (``train.StoreEvaluator`` /
+``train.StoreEvalStep``: gather, eval-mode encoder in one launch, ``feta_readout_eval``; ragged tails included, one host
+read per split).  Limits: no edge list is kept, so edge_index / batch / feature_indices of the tuple are None and a cheb
+model on a store without lhat has nothing to build its Laplacian from; the ragged tail batches of TRAINING go through
+``store.batch`` (repeated graphs would bias BatchNorm's batch statistics), and so does the evaluation of task 'sbm' and of
+stacks without a one-launch inference form (N_pad > 64); bf16 storage with filter_mode='cheb' is refused by the models, here
+as everywhere.
 """
 import time
 

@@ -1108,6 +1108,48 @@ typedef struct feta_gather_ex {
 } feta_gather_ex;
 int feta_batch_gather_ex(const feta_gather_ex* d, feta_stream_t stream);
 
+/* ---- graph-level readout of an evaluation batch: pooling, classifier, loss and metric terms in one launch ----------
+ * What the graph-level task shells run behind the encoder (masked mean pooling, Linear - activation - Linear:
+ * transformer/models.py) and the per-graph arithmetic of the reference's eval_epoch, forward only, for a batch that
+ * feta_batch_gather built: slot b holds the graph ids[b] of a split of G graphs.  For every slot b < *count with
+ * 0 <= ids[b] < G and 1 <= n_real[b] <= N (every other slot writes NOTHING):
+ *   pooled = mean of the rows y[i, b, :], i < n_real[b]        (row (i, b) starts at y + i * row_sn + b * row_sb)
+ *   h      = act(w1 pooled + b1), act(v) = v > 0 ? v : slope * v  (slope 0: ReLU; slope 1: the molhiv shell's identity)
+ *   scores[ids[b], 0..C) = w2 h + b2
+ *   terms[ids[b], 0..4) by loss_kind, from the slot's label (label_kind FETA_LABELS_GRAPH_F32 | FETA_LABELS_GRAPH_I64):
+ *     FETA_LOSS_L1          (|e|, e^2, 0, 1), e = logit - label                                            C = 1
+ *     FETA_LOSS_BCE_LOGITS  (bce, hit, 0, w): bce the binary cross entropy with logits, hit = (logit > 0) == (label > 0.5),
+ *                           w = 1; a NaN label (an unlabelled graph) gives bce = 0 and w = 0               C = 1
+ *     FETA_LOSS_CE          (-log softmax[label], argmax == label, 0, 1): log-sum-exp with the row maximum subtracted, the
+ *                           first index wins a tie; int64 labels; a label outside [0, C) gives (NaN, 0, 0, 1)
+ * count lives ON THE DEVICE, so a captured launch serves every batch length up to B; scores and terms are indexed by the
+ * graph's id in the split, so they do not depend on the order or the cut of the batches.  One workgroup per slot, no
+ * atomics, one summation order: a graph's results are bit-equal from launch to launch and from batch to batch.  16-byte
+ * loads where y (base and both strides), w1, w2 and terms are aligned for them. */
+#define FETA_LOSS_L1 0
+#define FETA_LOSS_BCE_LOGITS 1
+#define FETA_LOSS_CE 2
+typedef struct feta_readout {
+  const float* y;              /* encoder output rows, fp32, 64 dense columns */
+  int64_t row_sb, row_sn;      /* element strides of the graph and the node index ([N,B,64] contiguous: 64, 64 B) */
+  const int32_t* n_real;       /* [B] */
+  const int32_t* ids;          /* [B] graph id of each slot, device */
+  const int32_t* count;        /* [1] live slots, device */
+  const void* labels;          /* [B], label_kind */
+  const float* w1;             /* [64,64] */
+  const float* b1;             /* [64] or NULL */
+  const float* w2;             /* [C,64] */
+  const float* b2;             /* [C] or NULL */
+  float* scores;               /* [G,C] */
+  float* terms;                /* [G,4] */
+  int B, N, G, C, d_model;
+  int label_kind;              /* FETA_LABELS_GRAPH_F32 | FETA_LABELS_GRAPH_I64 */
+  int loss_kind;               /* FETA_LOSS_* */
+  float slope;
+} feta_readout;
+int feta_readout_eval_supported(int d_model, int C);   /* d_model = 64, 1 <= C <= 64 */
+int feta_readout_eval(const feta_readout* d, feta_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
