@@ -403,6 +403,23 @@ SIGNATURES['feta_readout_eval'] = ([C.POINTER(Readout), _S], C.c_int)
 
 LOSS_L1, LOSS_BCE_LOGITS, LOSS_CE = 0, 1, 2      # FETA_LOSS_*
 
+
+class ReadoutTrain(C.Structure):
+    """struct feta_readout_train (include/feta_hip.h) - field order must match the header."""
+    _fields_ = [
+        ('y', _F), ('row_sb', C.c_int64), ('row_sn', C.c_int64), ('n_real', _I), ('count', _I), ('labels', C.c_void_p),
+        ('w1', _F), ('b1', _F), ('w2', _F), ('b2', _F), ('scores', _F), ('loss', _F), ('ws', _F), ('dloss', _F),
+        ('dy', _F), ('drow_sb', C.c_int64), ('drow_sn', C.c_int64), ('dw1', _F), ('db1', _F), ('dw2', _F), ('db2', _F),
+        ('B', C.c_int), ('N', C.c_int), ('C', C.c_int), ('d_model', C.c_int),
+        ('label_kind', C.c_int), ('loss_kind', C.c_int), ('slope', C.c_float),
+    ]
+
+
+SIGNATURES['feta_readout_train_supported'] = ([C.c_int, C.c_int], C.c_int)
+SIGNATURES['feta_readout_train_ws_floats'] = ([C.c_int, C.c_int], C.c_int64)
+SIGNATURES['feta_readout_train_fwd'] = ([C.POINTER(ReadoutTrain), _S], C.c_int)
+SIGNATURES['feta_readout_train_bwd'] = ([C.POINTER(ReadoutTrain), _S], C.c_int)
+
 ABI_VERSION = 13
 
 
@@ -1135,6 +1152,39 @@ class Abi:
         d.label_kind, d.loss_kind, d.slope = label_kind, loss_kind, slope
         _fill(d, ptrs)
         self._check(self.lib.feta_readout_eval(C.byref(d), stream), 'feta_readout_eval')
+
+    def readout_train_supported(self, d_model, c):
+        return bool(self.lib.feta_readout_train_supported(d_model, c))
+
+    def readout_train_ws_floats(self, b, c):
+        return int(self.lib.feta_readout_train_ws_floats(b, c))
+
+    @staticmethod
+    def _readout_train_desc(b, n, c, d_model, row_sb, row_sn, label_kind, loss_kind, slope, ptrs):
+        _same_dtype(torch.float32, *(t for k, t in ptrs.items() if k not in ('n_real', 'count', 'labels')))
+        _same_dtype(torch.int32, ptrs.get('n_real'), ptrs.get('count'))
+        d = ReadoutTrain()
+        d.B, d.N, d.C, d.d_model, d.row_sb, d.row_sn = b, n, c, d_model, row_sb, row_sn
+        d.label_kind, d.loss_kind, d.slope = label_kind, loss_kind, slope
+        _fill(d, ptrs)
+        return d
+
+    def readout_train_fwd(self, b, n, c, stream, d_model=64, row_sb=0, row_sn=0, label_kind=LABELS_GRAPH_F32,
+                          loss_kind=LOSS_L1, slope=0.0, **ptrs):
+        """feta_readout_train_fwd (two launches): scores [b, c] by slot, loss [2] = (batch loss, 1 / sum of the weights)
+        and the workspace ws (readout_train_ws_floats(b, c) floats) of the live slots of a [b, n] batch.  Tensor-valued
+        keyword arguments become the descriptor's pointers (y, n_real, count, labels, w1, b1, w2, b2, scores, loss, ws)."""
+        d = self._readout_train_desc(b, n, c, d_model, row_sb, row_sn, label_kind, loss_kind, slope, ptrs)
+        self._check(self.lib.feta_readout_train_fwd(C.byref(d), stream), 'feta_readout_train_fwd')
+
+    def readout_train_bwd(self, b, n, c, stream, d_model=64, row_sb=0, row_sn=0, drow_sb=0, drow_sn=0,
+                          label_kind=LABELS_GRAPH_F32, loss_kind=LOSS_L1, slope=0.0, **ptrs):
+        """feta_readout_train_bwd (two launches) on the operands, loss and ws of readout_train_fwd: dloss [1] is the
+        incoming gradient of the loss, on the device; dy (rows with the strides drow_sb / drow_sn, written whole), dw1, db1,
+        dw2, db2: outputs, an output left out is skipped."""
+        d = self._readout_train_desc(b, n, c, d_model, row_sb, row_sn, label_kind, loss_kind, slope, ptrs)
+        d.drow_sb, d.drow_sn = drow_sb, drow_sn
+        self._check(self.lib.feta_readout_train_bwd(C.byref(d), stream), 'feta_readout_train_bwd')
 
 
 def bind(cdll):

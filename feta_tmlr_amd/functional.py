@@ -1150,3 +1150,84 @@ def readout_eval(y, n_real, ids, count, labels, w1, b1, w2, b2, scores, terms, l
                      label_kind=kind, loss_kind=LOSS_KINDS[loss_kind], slope=float(slope), y=y, n_real=n_real, ids=ids,
                      count=count, labels=labels, w1=w1, b1=b1, w2=w2, b2=b2, scores=scores, terms=terms)
     return scores, terms
+
+
+def _row_strides(t):
+    """(graph stride, node stride) in elements of a [N, B, d] tensor (the stride of a size-1 dim is arbitrary and multiplies
+    index 0 only)"""
+    return (t.stride(1) if t.shape[1] > 1 else 0), (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+class _ReadoutTrainFn(torch.autograd.Function):
+    """readout_train below: the forward is feta_readout_train_fwd, the backward feta_readout_train_bwd on the same
+    workspace; the incoming gradient of the loss stays on the device."""
+
+    @staticmethod
+    def forward(ctx, y, n_real, count, labels, w1, b1, w2, b2, loss_kind, slope):
+        abi, stream = _lib.backend(y, n_real, count, labels, w1, b1, w2, b2)
+        n, b, d = y.shape
+        c = w2.shape[0]
+        dev = y.device
+        scores = torch.empty((b, c), dtype=torch.float32, device=dev)
+        loss = torch.empty((2,), dtype=torch.float32, device=dev)
+        ws = torch.empty((abi.readout_train_ws_floats(b, c),), dtype=torch.float32, device=dev)
+        sb, sn = _row_strides(y)
+        ctx.kw = dict(d_model=d, row_sb=sb, row_sn=sn, loss_kind=loss_kind, slope=slope,
+                      label_kind=_abi.LABELS_GRAPH_F32 if labels.dtype == torch.float32 else _abi.LABELS_GRAPH_I64)
+        abi.readout_train_fwd(b, n, c, stream, y=y, n_real=n_real, count=count, labels=labels, w1=w1, b1=b1, w2=w2, b2=b2,
+                              scores=scores, loss=loss, ws=ws, **ctx.kw)
+        ctx.save_for_backward(y, n_real, count, labels, w1, b1, w2, b2, scores, loss, ws)
+        ctx.mark_non_differentiable(scores)
+        ctx.set_materialize_grads(False)      # (no launch that zero-fills a gradient for the scores)
+        return loss[0], scores
+
+    @staticmethod
+    def backward(ctx, dloss, _dscores):
+        if dloss is None:
+            return (None,) * 10
+        y, n_real, count, labels, w1, b1, w2, b2, scores, loss, ws = ctx.saved_tensors
+        abi, stream = _lib.backend(y, dloss)
+        n, b, d = y.shape
+        c = w2.shape[0]
+        need = ctx.needs_input_grad
+        new = lambda like, wanted: torch.empty(like.shape, dtype=torch.float32, device=y.device) if wanted else None
+        dy, dw1, dw2 = new(y, need[0]), new(w1, need[4]), new(w2, need[6])
+        db1 = new(b1, need[5]) if b1 is not None else None
+        db2 = new(b2, need[7]) if b2 is not None else None
+        dsb, dsn = _row_strides(dy) if dy is not None else (0, 0)
+        abi.readout_train_bwd(b, n, c, stream, drow_sb=dsb, drow_sn=dsn, y=y, n_real=n_real, count=count, labels=labels,
+                              w1=w1, b1=b1, w2=w2, b2=b2, scores=scores, loss=loss, ws=ws,
+                              dloss=dloss.to(torch.float32).reshape(1).contiguous(), dy=dy, dw1=dw1, db1=db1, dw2=dw2, db2=db2,
+                              **ctx.kw)
+        return dy, None, None, None, dw1, db1, dw2, db2, None, None
+
+
+def readout_train(y, n_real, count, labels, w1, b1, w2, b2, loss_kind, slope=0.0):
+    """Graph-level readout of a TRAINING batch (feta_readout_train_fwd / _bwd, two launches each): for every slot
+    b < count[0] the masked mean of the rows y[:n_real[b], b] ([N, B, 64] float32, any row strides), Linear(w1, b1) - act -
+    Linear(w2, b2) with act(v) = v if v > 0 else slope * v, and the batch loss of train.task_loss for ``loss_kind``
+    ('l1' | 'bce_logits' | 'ce') from labels[b] (float32 or int64): sum of the slots' terms over sum of their weights (a NaN
+    label under 'bce_logits' has weight 0; no labelled slot at all: NaN).  count (int32, one element) lives on the device.
+    -> (loss 0-d, scores [B, C]); the rows of scores from count[0] on are not written.  Differentiable in y, w1, b1, w2, b2
+    through the loss (scores carry no gradient); dy is zero in the padded rows and in the slots from count[0] on.  Under
+    torch.no_grad() only the forward launches run."""
+    if loss_kind not in LOSS_KINDS:
+        raise ValueError('unknown loss_kind %r' % (loss_kind,))
+    abi, _ = _lib.backend(y, n_real, count, labels, w1, b1, w2, b2)
+    if y.dim() != 3 or y.stride(2) != 1:
+        raise ValueError('readout_train: y must be [N, B, d] with dense columns, got %s with strides %s' % (tuple(y.shape), y.stride()))
+    n, b, d = y.shape
+    if w2.dim() != 2:
+        raise ValueError('readout_train: w2 must be [C, d], got %s' % (tuple(w2.shape),))
+    c = w2.shape[0]
+    if not abi.readout_train_supported(d, c):
+        raise ValueError('readout_train: d = %d, C = %d (the kernels have d = 64 and 1 <= C <= 64)' % (d, c))
+    for name, t, shape in (('n_real', n_real, (b,)), ('w1', w1, (d, d)), ('b1', b1, (d,)), ('w2', w2, (c, d)), ('b2', b2, (c,))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError('readout_train: %s must be contiguous %s, got %s' % (name, shape, tuple(t.shape)))
+    for name, t, least in (('count', count, 1), ('labels', labels, b)):
+        if t.numel() < least or not t.is_contiguous():
+            raise ValueError('readout_train: %s must be contiguous with at least %d elements' % (name, least))
+    if labels.dtype not in (torch.float32, torch.int64):
+        raise TypeError('readout_train: float32 or int64 labels, got %s' % labels.dtype)
+    return _ReadoutTrainFn.apply(y, n_real, count, labels, w1, b1, w2, b2, LOSS_KINDS[loss_kind], float(slope))

@@ -16,6 +16,8 @@ update captured once per padded size into a hipGraph and replayed - the referenc
 launches and a host sync (`.cpu()` at transformer/models.py:246) per step.  ``StoreTrainStep`` feeds it from a
 device-resident split, and ``StoreEvaluator`` / ``StoreEvalStep`` are the eval_epoch of the graph-level tasks in the
 same form: one captured forward-only graph per bucket, one host read per split (``evaluate`` is the eager form).
+``fused_head=True`` (task_loss, train_step, GraphedTrainStep, StoreTrainStep; default off) runs pooling, classifier, loss and
+their backward of a graph-level shell as the four launches of ``functional.readout_train``.
 """
 import torch
 from torch import nn
@@ -75,12 +77,33 @@ def pad_node_labels(labels, feature_indices, bsz, n_pad):
     return out
 
 
-def task_loss(task, model, criterion, batch9, graph_cache=None, padded_node_labels=False):
+def task_loss(task, model, criterion, batch9, graph_cache=None, padded_node_labels=False, fused_head=False, count=None):
     """forward + loss of one collated batch; returns (loss, model output).
     padded_node_labels ('sbm'): labels are [B, N_pad] from pad_node_labels and the model returns the
     logits of every position - the same mean over the real nodes as the reference's boolean gather
-    (transformer/models.py:1070-1071) with static shapes and no host sync."""
+    (transformer/models.py:1070-1071) with static shapes and no host sync.
+    fused_head: the body is ``model.encoder_rows`` and ``functional.readout_train`` - pooling, classifier and loss in two
+    launches, their backward in two - for what ``_fused_head_plan`` accepts (ValueError otherwise).  The second result is then
+    the scores [B, C] of the readout on EVERY task, without a gradient.  On the default path it is whatever the shell returns:
+    [B, C] from the 'zinc' / 'tu' shell ([B, 1] for one output) and the SQUEEZED logits [B] (0-d for B = 1) from the molhiv
+    shell, which returns ``cls_out.squeeze()``.
+    count (fused_head only): int32 device tensor of one element, the number of leading slots that count for the loss and get
+    a gradient (StoreTrainStep's padded batches); default: all B."""
     x, mask, pe, lap_pe, degree, labels, edge_index, batch, feature_indices = batch9
+    if fused_head:
+        from . import functional as FF
+        from .transformer.layers import n_real_from_mask
+        kind, slope = _fused_head_plan(task, model, criterion)
+        rows, _ = model.encoder_rows(x, edge_index, batch, feature_indices, mask, pe, lap_pe, degree, graph_cache=graph_cache)
+        n_real = graph_cache.n_real if graph_cache is not None and graph_cache.n_real is not None else n_real_from_mask(mask)
+        if count is None:
+            count = torch.full((1,), x.shape[0], dtype=torch.int32, device=x.device)
+        labels = labels.reshape(-1)
+        if labels.dtype != torch.int64:
+            labels = labels.float()
+        head = model.classifier
+        return FF.readout_train(rows, n_real, count, labels.contiguous(), head[0].weight, head[0].bias, head[2].weight,
+                                head[2].bias, kind, slope)
     extra = {'padded_logits': True} if padded_node_labels else {}
     res = model(x, edge_index, batch, feature_indices, mask, pe, lap_pe, degree,
                 graph_cache=graph_cache, **extra)
@@ -108,14 +131,17 @@ def task_loss(task, model, criterion, batch9, graph_cache=None, padded_node_labe
     return criterion(output, labels), output
 
 
-def train_step(task, model, criterion, optimizer, batch9, graph_cache=None, lr=None, padded_node_labels=False):
+def train_step(task, model, criterion, optimizer, batch9, graph_cache=None, lr=None, padded_node_labels=False,
+               fused_head=False):
     """One iteration of the reference's train_epoch loop body.  -> loss (0-d tensor, no sync).
-    padded_node_labels: as task_loss (batches of transformer.store.DeviceGraphStore.batch carry node labels padded)."""
+    padded_node_labels: as task_loss (batches of transformer.store.DeviceGraphStore.batch carry node labels padded).
+    fused_head: as task_loss (pooling, classifier, loss and their backward in functional.readout_train)."""
     if lr is not None:
         for group in optimizer.param_groups:
             group['lr'] = lr
     optimizer.zero_grad(set_to_none=True)
-    loss, _ = task_loss(task, model, criterion, batch9, graph_cache, padded_node_labels=padded_node_labels)
+    loss, _ = task_loss(task, model, criterion, batch9, graph_cache, padded_node_labels=padded_node_labels,
+                        fused_head=fused_head)
     loss.backward()
     optimizer.step()
     from .functional import DropoutState
@@ -158,10 +184,17 @@ class GraphedTrainStep:
     the example batch, so the parameters, the module buffers (BatchNorm running statistics,
     num_batches_tracked) and the optimiser state (moments and step counters) are snapshotted before
     and restored, in place, afterwards - an instance created mid-training (one per padded-size bucket)
-    leaves the trajectory exactly where the reference loop would have it."""
+    leaves the trajectory exactly where the reference loop would have it.
 
-    def __init__(self, task, model, criterion, optimizer, batch9, graph_cache=None, warmup_iters=3):
+    fused_head: the step's head is functional.readout_train (task_loss); ValueError at construction for what
+    ``_fused_head_plan`` refuses."""
+
+    def __init__(self, task, model, criterion, optimizer, batch9, graph_cache=None, warmup_iters=3, fused_head=False):
         self.task, self.model, self.criterion, self.optimizer = task, model, criterion, optimizer
+        self.fused_head, self.count = bool(fused_head), None
+        if fused_head:
+            _fused_head_plan(task, model, criterion)
+            self.count = torch.full((1,), batch9[0].shape[0], dtype=torch.int32, device=batch9[0].device)
         for group in optimizer.param_groups:
             if not group.get('capturable', False):
                 raise ValueError('GraphedTrainStep needs make_optimizer(..., capturable=True)')
@@ -238,7 +271,7 @@ class GraphedTrainStep:
     def _body(self):
         self.optimizer.zero_grad(set_to_none=True)
         loss, _ = task_loss(self.task, self.model, self.criterion, self.static, self.cache,
-                            padded_node_labels=self.task == 'sbm')
+                            padded_node_labels=self.task == 'sbm', fused_head=self.fused_head, count=self.count)
         loss.backward()
         self.optimizer.step()
         from .functional import DropoutState
@@ -277,20 +310,32 @@ class StoreTrainStep(GraphedTrainStep):
 
     One instance per (bucket n_pad, batch_size); the same snapshot / restore contract, set_lr and DropoutState device
     mode as GraphedTrainStep (construction does not advance training: the warm-up and capture steps run on
-    ``example_ids``, default the first graphs of the bucket).  Only FULL batches are captured: the ragged last batch of
-    a bucket goes through ``store.batch(ids)`` and ``train_step(..., padded_node_labels=task == 'sbm')``.
+    ``example_ids``, default the first graphs of the bucket).  Without ``fused_head`` (below) only FULL batches go through the
+    captured step: the ragged last batch of a bucket goes through ``store.batch(ids)`` and
+    ``train_step(..., padded_node_labels=task == 'sbm')``.
     filter_mode='spectral' reads the store's u / lam, filter_mode='cheb' its lhat (``DeviceGraphStore(..., lhat=True)``;
     the gather launch is then feta_batch_gather_ex), with either setting of heads_share_graph.
     lap_sign_flip: the reference's random sign per Laplacian-PE column (lap_sign_flip above), drawn on the host for every
     ``step(ids)`` with ``lap_signs(lap_dim, generator)`` and applied by the gather launch inside the hipGraph: one more
     host-to-device copy of 4 * lap_dim bytes per step.  Warm-up and capture run with signs of +1 and draw nothing.
     dtype: storage type of x and pe as the gather emits them; the task shells embed fp32 x, so they keep float32 (a
-    bf16-storage model rounds its rows and pe itself) and torch.bfloat16 is for a model that consumes bf16 x directly."""
+    bf16-storage model rounds its rows and pe itself) and torch.bfloat16 is for a model that consumes bf16 x directly.
+
+    fused_head: the head of the captured step is functional.readout_train (task_loss), which reads the number of live slots
+    on the device, so ``step(ids)`` also takes a RAGGED batch, 1 <= len(ids) <= batch_size (host sequence or device tensor),
+    as StoreEvalStep does: the static id buffer holds batch_size + 1 int32, the ids and behind them the count; a short batch
+    is padded with ids[0], and host ids and count travel in the one pinned copy.  The padded slots run through the encoder,
+    count for nothing in the loss and get a zero gradient, and every gradient is linear in the readout's: the step equals
+    an eager step on the short batch up to summation order.  NOT with a BatchNorm module in training mode, whose batch
+    statistics would see the repeated graph: such a model keeps the ValueError for a short batch."""
 
     def __init__(self, task, model, criterion, optimizer, store, n_pad, batch_size, dtype=torch.float32,
-                 example_ids=None, warmup_iters=3, lap_sign_flip=False, generator=None):
+                 example_ids=None, warmup_iters=3, lap_sign_flip=False, generator=None, fused_head=False):
         from .transformer.store import GatherBuffers
         self.task, self.model, self.criterion, self.optimizer = task, model, criterion, optimizer
+        self.fused_head, self.count = bool(fused_head), None
+        if fused_head:
+            _fused_head_plan(task, model, criterion)
         mode = getattr(model.encoder, 'filter_mode', 'spectral')
         if mode not in ('spectral', 'cheb'):
             raise ValueError("StoreTrainStep runs filter_mode='spectral' and 'cheb' models, got %r" % (mode,))
@@ -305,6 +350,10 @@ class StoreTrainStep(GraphedTrainStep):
             if not torch.is_tensor(group['lr']):
                 group['lr'] = torch.tensor(float(group['lr']), device=store.device)
         self.bufs = GatherBuffers(store, batch_size, n_pad, dtype, lhat=mode == 'cheb', lap_sign=bool(lap_sign_flip))
+        self.ids = self.bufs.ids
+        if fused_head:      # one static buffer: the gather reads its front, the readout the count behind it
+            self.ids = torch.zeros((self.bufs.bsz + 1,), dtype=torch.int32, device=store.device)
+            self.bufs.ids, self.count = self.ids[:self.bufs.bsz], self.ids[self.bufs.bsz:]
         self._pinned, self._copied, self._turn = [None, None], [None, None], 0
         if example_ids is None:
             members = store.bucket_ids(n_pad)
@@ -331,11 +380,24 @@ class StoreTrainStep(GraphedTrainStep):
     def _set_ids(self, ids, signs=None):
         import numpy as np
         ids = self.store.device_ids(ids) if torch.is_tensor(ids) else np.asarray(ids, np.int32)
-        if tuple(ids.shape) != (self.bufs.bsz,):
-            raise ValueError('this step was captured for exactly %d ids, got %s (a ragged batch goes through '
-                             'store.batch and train_step)' % (self.bufs.bsz, tuple(ids.shape)))
+        bsz = self.bufs.bsz
+        if tuple(ids.shape) != (bsz,):
+            if not self.fused_head:
+                raise ValueError('this step was captured for exactly %d ids, got %s (a ragged batch goes through '
+                                 'store.batch and train_step)' % (bsz, tuple(ids.shape)))
+            if ids.ndim != 1 or not 1 <= ids.shape[0] <= bsz:
+                raise ValueError('this step takes 1 to %d ids, got %s' % (bsz, tuple(ids.shape)))
+            if any(isinstance(m, nn.modules.batchnorm._BatchNorm) and m.training for m in self.model.modules()):
+                raise ValueError('this step was captured for exactly %d ids, got %s: a short batch is padded with ids[0], and '
+                                 'the batch statistics of a BatchNorm module in training mode would see the repeated graph '
+                                 '(a ragged batch goes through store.batch and train_step)' % (bsz, tuple(ids.shape)))
+        k = ids.shape[0]
         if torch.is_tensor(ids):
-            self.bufs.ids.copy_(ids, non_blocking=True)
+            self.bufs.ids[:k].copy_(ids, non_blocking=True)
+            if self.fused_head:     # (device operands only: nothing waits for the host)
+                if k < bsz:
+                    self.bufs.ids[k:].copy_(ids[:1].expand(bsz - k), non_blocking=True)
+                self.count.fill_(k)
             if signs is None:
                 return
         # one asynchronous host-to-device copy per host operand (the ids, the signs), straight into the static buffer,
@@ -345,14 +407,18 @@ class StoreTrainStep(GraphedTrainStep):
         self._turn ^= 1
         if self._pinned[turn] is None:
             sign_buf = None if self.bufs.lap_sign is None else torch.empty(self.bufs.lap_sign.shape, pin_memory=True)
-            self._pinned[turn] = (torch.empty(self.bufs.bsz, dtype=torch.int32, pin_memory=True), sign_buf)
+            self._pinned[turn] = (torch.empty(self.ids.numel(), dtype=torch.int32, pin_memory=True), sign_buf)
             self._copied[turn] = torch.cuda.Event()
         else:
             self._copied[turn].synchronize()
         id_buf, sign_buf = self._pinned[turn]
         if not torch.is_tensor(ids):
-            id_buf.numpy()[:] = ids
-            self.bufs.ids.copy_(id_buf, non_blocking=True)
+            host = id_buf.numpy()
+            host[:k] = ids
+            if self.fused_head:
+                host[k:bsz] = ids[0]
+                host[bsz] = k
+            self.ids.copy_(id_buf, non_blocking=True)
         if signs is not None:
             sign_buf.copy_(signs)
             self.bufs.lap_sign.copy_(sign_buf, non_blocking=True)
@@ -442,37 +508,60 @@ def _evaluate(task, model, criterion, batches):
 _USE_EAGER = 'run it through store.batch and train.evaluate'
 
 
-def _readout_plan(task, model, criterion, store):
-    """-> (loss_kind of functional.readout_eval, slope of the classifier's activation, d_model, nb_class, filter_mode) of a
-    graph-level shell whose evaluation a StoreEvalStep on ``store`` can run; ValueError where it cannot (everything that
-    does not depend on the padded size)."""
+_USE_PLAIN_HEAD = 'run it with fused_head=False'
+
+
+def _head_plan(task, model, criterion, instead):
+    """-> (loss_kind of functional.readout_eval / readout_train, slope of the classifier's activation, d_model, nb_class) of a
+    graph-level shell and its criterion: the part of _readout_plan and _fused_head_plan that looks at the model and the
+    criterion only.  ValueError, ending with ``instead`` (the path to take), for what the readout kernels do not compute."""
     if task == 'sbm':
-        raise ValueError("task 'sbm' has node-level logits and a per-batch confusion-matrix accuracy: " + _USE_EAGER)
+        raise ValueError("task 'sbm' has node-level logits and a per-batch confusion-matrix accuracy: " + instead)
     if task not in ('zinc', 'tu', 'molhiv'):
         raise ValueError('unknown task %r' % (task,))
     head = getattr(model, 'classifier', None)
     if (not hasattr(model, 'encoder_rows') or not isinstance(head, nn.Sequential) or len(head) != 3
             or not isinstance(head[0], nn.Linear) or not isinstance(head[2], nn.Linear)):
-        raise ValueError('the model is not a graph-level shell with a Linear - activation - Linear classifier: ' + _USE_EAGER)
+        raise ValueError('the model is not a graph-level shell with a Linear - activation - Linear classifier: ' + instead)
     if isinstance(head[1], nn.ReLU):
         slope = 0.0
     elif isinstance(head[1], nn.LeakyReLU):
         slope = float(head[1].negative_slope)        # (nn.LeakyReLU(True) of the molhiv shell: 1.0, the identity)
     else:
-        raise ValueError('classifier activation %s: ReLU or LeakyReLU only; %s' % (type(head[1]).__name__, _USE_EAGER))
+        raise ValueError('classifier activation %s: ReLU or LeakyReLU only; %s' % (type(head[1]).__name__, instead))
     d, c = head[0].in_features, head[2].out_features
     kind = 'l1' if task == 'zinc' else 'bce_logits' if (task == 'molhiv' or c == 1) else 'ce'
     if criterion is not None and task != 'molhiv':       # (task_loss does not read the criterion of 'molhiv')
         want = {'l1': nn.L1Loss, 'bce_logits': nn.BCEWithLogitsLoss, 'ce': nn.CrossEntropyLoss}[kind]
         if not isinstance(criterion, want):
             raise ValueError('task %r with %d outputs is evaluated with %s, got %s: %s'
-                             % (task, c, want.__name__, type(criterion).__name__, _USE_EAGER))
+                             % (task, c, want.__name__, type(criterion).__name__, instead))
         if (getattr(criterion, 'weight', None) is not None or getattr(criterion, 'pos_weight', None) is not None
                 or getattr(criterion, 'label_smoothing', 0.0) != 0.0):
-            raise ValueError('a criterion with class weights or label smoothing: ' + _USE_EAGER)
+            raise ValueError('a criterion with class weights or label smoothing: ' + instead)
         if criterion.reduction != 'mean':
             raise ValueError("a criterion with reduction %r (the evaluation averages per batch: 'mean'): %s"
-                             % (criterion.reduction, _USE_EAGER))
+                             % (criterion.reduction, instead))
+    return kind, slope, d, c
+
+
+def _fused_head_plan(task, model, criterion):
+    """-> (loss_kind, slope) of functional.readout_train for a graph-level shell that task_loss(..., fused_head=True) can run:
+    a Linear - ReLU / LeakyReLU - Linear classifier with d_model = 64 and at most 64 outputs under the task's own loss with
+    reduction 'mean', no class weights, pos_weight or label smoothing; ValueError otherwise."""
+    kind, slope, d, c = _head_plan(task, model, criterion, _USE_PLAIN_HEAD)
+    from . import _lib
+    if not _lib.backend(model.classifier[0].weight)[0].readout_train_supported(d, c):
+        raise ValueError('feta_readout_train has d_model = 64 and at most 64 outputs, the classifier has %d and %d: %s'
+                         % (d, c, _USE_PLAIN_HEAD))
+    return kind, slope
+
+
+def _readout_plan(task, model, criterion, store):
+    """-> (loss_kind of functional.readout_eval, slope of the classifier's activation, d_model, nb_class, filter_mode) of a
+    graph-level shell whose evaluation a StoreEvalStep on ``store`` can run; ValueError where it cannot (everything that
+    does not depend on the padded size)."""
+    kind, slope, d, c = _head_plan(task, model, criterion, _USE_EAGER)
     from . import _lib
     if not _lib.backend(store.x)[0].readout_eval_supported(d, c):
         raise ValueError('feta_readout_eval has d_model = 64 and at most 64 outputs, the classifier has %d and %d: %s'

@@ -1150,6 +1150,60 @@ typedef struct feta_readout {
 int feta_readout_eval_supported(int d_model, int C);   /* d_model = 64, 1 <= C <= 64 */
 int feta_readout_eval(const feta_readout* d, feta_stream_t stream);
 
+/* ---- graph-level readout of a TRAINING batch: pooling, classifier, loss and their backward in four launches ---------
+ * The training counterpart of feta_readout_eval: the same pooled / h / logits arithmetic per slot (the same device
+ * code), the batch loss of train.task_loss on the device, and the backward of all of it.  A slot b is LIVE when
+ * b < *count and 1 <= n_real[b] <= N; a slot b < *count with another n_real is read as an empty graph (zero scores, term
+ * and weight 0, zero gradient).  Slots b >= *count write nothing in the forward.
+ *
+ * feta_readout_train_fwd, two launches (one workgroup per slot, then one workgroup for the loss):
+ *   scores[b, 0..C) = w2 h + b2                                                        (by SLOT, not by graph id)
+ *   (term_b, weight_b) = the first and the last loss term of feta_readout_eval for loss_kind and the slot's label
+ *   loss[0] = (sum_b term_b) / (sum_b weight_b), loss[1] = 1 / sum_b weight_b          (b < *count, ascending;
+ *                                                                                        sum weight = 0: NaN and inf)
+ *   ws: per slot pooled, the pre-activation z = w1 pooled + b1, the unscaled dlogit, (term, weight)
+ *     dlogit  FETA_LOSS_L1 sign(e) with sign(0) = 0 | FETA_LOSS_BCE_LOGITS (sigmoid(x) - label) weight_b |
+ *             FETA_LOSS_CE softmax - onehot (a label outside [0, C): NaN)
+ * feta_readout_train_bwd, two launches (one workgroup per slot, then the parameter gradients), after the forward on the
+ * same descriptor and ws; *dloss is the incoming gradient of loss[0], read ON THE DEVICE:
+ *   s = *dloss * loss[1];  dl = s dlogit;  dz = (w2^T dl) * (z > 0 ? 1 : slope);  dpooled = w1^T dz
+ *   dy[i, b, :] = dpooled / n_real[b] for i < n_real[b] of a live slot, ZERO in every other row of every slot b < B
+ *   dw1 = sum_b dz_b (x) pooled_b, db1 = sum_b dz_b, dw2 = sum_b dl_b (x) h_b, db2 = sum_b dl_b   (b < *count, ascending)
+ *   dy, dw1, db1, dw2, db2: NULL skips the output.  The parameter gradients are tiled over output rows (16 per
+ *   workgroup) and walk the slots in chunks of 64.
+ * No atomics, no library call, one summation order: two runs on the same operands are bit-equal.  ws holds
+ * feta_readout_train_ws_floats(B, C) floats, 16-byte aligned, caller-owned, and must survive from the forward to the
+ * backward.  16-byte accesses where y / dy (base and both strides), w1 and w2 are aligned for them. */
+typedef struct feta_readout_train {
+  const float* y;              /* encoder output rows, fp32, 64 dense columns */
+  int64_t row_sb, row_sn;      /* element strides of y's graph and node index */
+  const int32_t* n_real;       /* [B] */
+  const int32_t* count;        /* [1] live slots, device */
+  const void* labels;          /* [B], label_kind */
+  const float* w1;             /* [64,64] */
+  const float* b1;             /* [64] or NULL */
+  const float* w2;             /* [C,64] */
+  const float* b2;             /* [C] or NULL */
+  float* scores;               /* [B,C] */
+  float* loss;                 /* [2]: the batch loss, 1 / sum of the weights */
+  float* ws;                   /* feta_readout_train_ws_floats(B, C) floats */
+  const float* dloss;          /* [1] gradient of loss[0], device (backward only) */
+  float* dy;                   /* backward: [N,B,64] rows with the strides below, or NULL */
+  int64_t drow_sb, drow_sn;
+  float* dw1;                  /* backward: [64,64] or NULL */
+  float* db1;                  /* backward: [64] or NULL */
+  float* dw2;                  /* backward: [C,64] or NULL */
+  float* db2;                  /* backward: [C] or NULL */
+  int B, N, C, d_model;
+  int label_kind;              /* FETA_LABELS_GRAPH_F32 | FETA_LABELS_GRAPH_I64 */
+  int loss_kind;               /* FETA_LOSS_* */
+  float slope;
+} feta_readout_train;
+int feta_readout_train_supported(int d_model, int C);   /* d_model = 64, 1 <= C <= 64 */
+int64_t feta_readout_train_ws_floats(int B, int C);
+int feta_readout_train_fwd(const feta_readout_train* d, feta_stream_t stream);
+int feta_readout_train_bwd(const feta_readout_train* d, feta_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

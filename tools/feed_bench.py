@@ -15,6 +15,8 @@ same store's launch without lhat).  `--shape molhiv` (B = 1024, one N_pad = 64 b
 `gather` leg only: its leg A aborted on the MI355X at interpreter exit the one time it was run, the cause is not known,
 and the training legs of that shape are refused until it is (EXPERIMENTS.md).  One leg per process and one JSON line per
 process; `--all` runs the legs alternately in fresh child processes, --runs times each, and prints medians and raw values.
+`--fused-head` builds leg B's StoreTrainStep with fused_head=True (pooling, classifier, loss and their backward in
+functional.readout_train, four launches); legs A, C and gather do not change.
 """
 import argparse
 import json
@@ -37,6 +39,7 @@ ap.add_argument('--filter-mode', default='spectral', choices=['spectral', 'cheb'
                 help="cheb: the Chebyshev recursion on Lhat - the store keeps lhat and no eigenpairs (f32 storage only)")
 ap.add_argument('--all', action='store_true', help='legs A, B, C (and gather once) in fresh processes, alternating')
 ap.add_argument('--runs', type=int, default=3)
+ap.add_argument('--fused-head', action='store_true', help='leg B: StoreTrainStep(..., fused_head=True)')
 args = ap.parse_args()
 B = args.batch or (128 if args.shape == 'zinc' else 1024)
 N_PAD = 37 if args.shape == 'zinc' else 64
@@ -50,7 +53,7 @@ if args.all:
     raw = {'A': [], 'B': [], 'C': []}
     extra = {}
     base = [sys.executable, os.path.abspath(__file__), '--shape', args.shape, '--steps', str(args.steps), '--batch', str(B),
-            '--dtype', args.dtype, '--filter-mode', args.filter_mode]
+            '--dtype', args.dtype, '--filter-mode', args.filter_mode] + (['--fused-head'] if args.fused_head else [])
     for leg in ['gather'] + ['A', 'B', 'C'] * args.runs:
         out = subprocess.run(base + ['--leg', leg], capture_output=True, text=True, timeout=900)
         if out.returncode != 0:       # nothing more is started on the device after a failure
@@ -63,7 +66,7 @@ if args.all:
             raw[leg].append(res['ms_per_step'])
     med = {k: statistics.median(v) for k, v in raw.items()}
     print(json.dumps(dict(shape=args.shape, dtype=args.dtype, filter_mode=args.filter_mode, batch=B, n_pad=N_PAD,
-                          steps=args.steps, raw_ms=raw, median_ms=med,
+                          steps=args.steps, fused_head=args.fused_head, raw_ms=raw, median_ms=med,
                           graphs_per_s={k: B / (v * 1e-3) for k, v in med.items()},
                           b_slowest_vs_a_fastest=(max(raw['B']), min(raw['A'])), b_minus_c_ms=med['B'] - med['C'],
                           c_spread_ms=max(raw['C']) - min(raw['C']), gather_us=extra.get('gather_us'),
@@ -123,6 +126,8 @@ def timed(step):
 
 res = dict(leg=args.leg, shape=args.shape, dtype=args.dtype, filter_mode=args.filter_mode, batch=B, n_pad=N_PAD,
            steps=args.steps)
+if args.leg == 'B':
+    res['fused_head'] = args.fused_head
 if args.leg in ('A', 'C'):
     stager = D.BatchStager(packed, B, N_PAD, dev, **opts)
     batch9, cache = stager.stage(id_sets[0])
@@ -138,7 +143,7 @@ else:
     res.update(store_build_s=store.build_seconds, store_nbytes=store.nbytes,
                store_bytes_per_graph=store.nbytes / store.num_graphs)
     if args.leg == 'B':
-        step = T.StoreTrainStep(task, model, crit, opt, store, N_PAD, B)
+        step = T.StoreTrainStep(task, model, crit, opt, store, N_PAD, B, fused_head=args.fused_head)
         step.set_lr(1e-3)
         ms = timed(step)
         dev_sets = [store.device_ids(ids) for ids in id_sets]
